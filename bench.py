@@ -27,7 +27,15 @@ Output: ONE line on stdout, the bench line of the contract, compact: its `roofli
 both kernels' rooflines plus the decode / prefill fractions of the dynamic legs; `legs` is a digest of the legs outside the timed
 region.  Every leg in full goes to stderr as one {"details": {...}} line.
 
-Every line (every N, static or dynamic) carries:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: set up, W warm-up steps (the first is
+reported as `cold_wave`), K timed steps, the line.  `value` (tokens/s), `ms_per_step` and the rooflines of the kernels timed inside those
+steps are always there.  Everything else below — `clock_mhz_mean` / `power_w_mean`, `cpu_baseline`, `roofline.other.power_ceiling` /
+`hbm_ceiling`, the legs outside the timed region, `scaling_reference` and `legs.scale_series` — takes `--full`.
+`--dump-outputs DIR` writes what the callers of the timed path received in the LAST timed step: DIR/attention_out.npy (float32, the
+last layer's attention output of every iteration, at most 16 evenly spaced rows of each) and DIR/attention_out_rows.npy (float64:
+iteration, row), `_rankR` appended for N > 1; q/k/v come from a seeded generator, so the same arguments give the same inputs.
+
+With --full, every line (every N, static or dynamic) carries:
   `roofline`          the kernel with the largest summed time on this rank: ALGORITHMIC work of the timed launches / their summed
                       duration, from HIP events on the launch stream inside the timed region (every launch for the static
                       workloads, every 8th for the dynamic replay, whose launches are ragged: work is accounted per launch);
@@ -50,7 +58,7 @@ Every line (every N, static or dynamic) carries:
   `legs.scale_series` ONE fixed workload at every N — Yi-34B (56 / 8 heads / N, 60 layers), one 131 072-token request in 16 k chunks — so that tokens/s
                       across the N = 1 / 2 / 4 / 8 lines is a strong-scaling series (the lines' `value`s follow BASELINE.json's per-N configs);
                       N > 1 adds `scaling_reference`: the same step once more WITHOUT the control-plane exchange (= --rank-of N on one GPU).
-N = 1 adds, outside the timed region: `cold_wave`, `full_trace_50req`, `dynamic` (configs[2] shape, closed loop, time-weighted KV
+N = 1 with --full adds, outside the timed region: `full_trace_50req`, `dynamic` (configs[2] shape, closed loop, time-weighted KV
 utilisation), `dynamic_tp8_rank` (the TP8 rank shape: 256 sequences resident at full depth, deferred reclamation on / off),
 `c4_rank_share_128k` (ONE rank's share of configs[3]'s 128 k request: Yi-34B TP2 heads, 16 k chunks — the metric's 128 k half on one
 GPU), `hybrid_sarathi` (Sarathi-scheduled hybrid batches: serial order vs prefill || decode on two streams), `open_loop` (Poisson
@@ -117,7 +125,14 @@ def parse():
     ap.add_argument("--per-piece-prefill", action="store_true", help="A/B: NO persistent workgroups anywhere (prefill64p_kernel off); NOT the bench line")
     ap.add_argument("--persistent-prefill", action="store_true", help="A/B: EVERY prefill work list through persistent workgroups; NOT the bench line")
     ap.add_argument("--qps", type=float, default=0.0, help="run ONLY the open-loop replay (Poisson arrivals, reference recipe) at this rate and print it")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: clock / power telemetry, the legs outside "
+                    "the timed region, the measured power / HBM ceilings, the CPU baselines (N = 1) and the scaling reference / scale series (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write a fixed sample of the attention outputs of the last timed step to "
+                    "DIR/*.npy (float32 values, float64 row index; at most 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def valid_or_dry(a) -> bool:
@@ -298,6 +313,55 @@ def _emit(line: str):
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (line + "\n").encode())
 
 
+DUMP_BYTES = 64 << 20           # --dump-outputs: everything written, all ranks together
+
+
+class OutputTap:
+    """--dump-outputs: what the callers of runner.run_iteration receive — the attention output of the last layer, [T, Hq * D] — sampled
+    while one step runs.  Every iteration keeps at most ROWS of its T rows, evenly spaced (rows 0, s, 2s, ... with s = T // ROWS), copied
+    on the compute stream right behind the kernels that wrote them; nothing is read back until the step has ended."""
+    ROWS = 16
+
+    def __init__(self, runner):
+        self.runner, self.orig = runner, runner.run_iteration
+        self.parts, self.rows = [], []
+        runner.run_iteration = self._run
+
+    def _run(self, mds):
+        import torch
+        out = self.orig(mds)
+        T = out.shape[0]
+        k = min(T, self.ROWS)
+        s = T // k
+        with torch.cuda.stream(self.runner.stream):
+            self.parts.append(out[::s][:k].clone())
+        it = len(self.parts) - 1
+        self.rows += [(it, s * j) for j in range(k)]
+        return out
+
+    def close(self):
+        self.runner.run_iteration = self.orig
+
+    def write(self, path, suffix="", budget=DUMP_BYTES):
+        """DIR/attention_out{suffix}.npy: float32 [R, Hq * D], the sampled rows in issue order; DIR/attention_out_rows{suffix}.npy: float64
+        [R, 2], (iteration of the step, row of that iteration's output) of each.  Over `budget`, a seeded subset of the rows is kept."""
+        import numpy as np
+        import torch
+        out = torch.cat(self.parts)
+        if out.is_cuda:
+            torch.cuda.synchronize()          # the copies were queued on the runner's (non-blocking) stream
+        out = out.float().cpu().numpy()
+        rows = np.asarray(self.rows, dtype=np.float64).reshape(-1, 2)
+        per_row = out.shape[1] * 4 + 16
+        if out.shape[0] * per_row > budget:
+            keep = np.sort(np.random.default_rng(0).choice(out.shape[0], budget // per_row, replace=False))
+            out, rows = out[keep], rows[keep]
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "attention_out%s.npy" % suffix), out)
+        np.save(os.path.join(path, "attention_out_rows%s.npy" % suffix), rows)
+        self.parts, self.rows = [], []
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -455,17 +519,25 @@ def main():
     vm0 = vattention.stats()
     pairs["pf"] = pairs["dc"] = 0.0
     enable_op_timers(True, every=TIMER_EVERY[w["mode"]])      # HIP events on the launch stream, inside the timed region
-    from vattention_amd.telemetry import Sampler
-    sampler = Sampler(local, 0.1).__enter__() if rank == 0 else None      # a side process: shader clock and board power
+    sampler = None
+    if a.full and rank == 0:
+        from vattention_amd.telemetry import Sampler
+        sampler = Sampler(local, 0.1).__enter__()      # a side process: shader clock and board power
     barrier()
     wall0 = time.time()
     t0 = time.perf_counter()
     tokens = 0
-    for _ in range(a.steps):
+    tap = None
+    for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            tap = OutputTap(runner)
         tokens += one_step()
     barrier()
     dt = time.perf_counter() - t0
     telemetry = sampler.window(wall0, time.time()) if sampler is not None else None
+    if tap is not None:
+        tap.close()
+        tap.write(a.dump_outputs, "_rank%d" % rank if world > 1 else "", DUMP_BYTES // world)
     detail = drain_op_timers_detail()
     enable_op_timers(False)
     vm1 = vattention.stats()
@@ -530,7 +602,7 @@ def main():
     # that = what the exchange and the ranks' skew cost.  (b) `scale_series` — the fixed Yi-34B 128 k request at this N (the main
     # workload itself at N = 2 / 4; run here at N = 8) ----
     scaling_reference = series = None
-    if dist is not None and valid_or_dry(a):
+    if dist is not None and a.full and valid_or_dry(a):
         hook_saved, runner.iter_hook = runner.iter_hook, None
         pairs_saved = dict(pairs)                        # (the cpu_baseline scales by the pairs of the TIMED steps)
         barrier()
@@ -563,7 +635,7 @@ def main():
 
     # ---- N = 1 extras, outside the timed region ----
     extras = {}
-    if world == 1 and valid and not a.no_dynamic:
+    if world == 1 and valid and a.full and not a.no_dynamic:
         torch.cuda.synchronize()
         try:
             runner.stats.__init__()
@@ -681,7 +753,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not a.no_power_ceiling and not a.leg and isinstance((out.get("roofline") or {}).get("other"), dict):
+        if world == 1 and a.full and not a.no_power_ceiling and not a.leg and isinstance((out.get("roofline") or {}).get("other"), dict):
             pf, dc = out["roofline"]["other"].get("prefill") or {}, out["roofline"]["other"].get("decode") or {}
             pc, hc = measured_ceilings(pf.get("achieved") if pf.get("unit") == "TFLOP/s" else None, dc.get("achieved") if dc.get("unit") == "GB/s" else None)
             out["roofline"]["other"]["power_ceiling"], out["roofline"]["other"]["hbm_ceiling"] = pc, hc
@@ -691,7 +763,7 @@ def main():
                 out["roofline"]["frac_of_measured_ceiling"] = over
                 out["roofline"]["measured_ceiling"] = ("back-to-back MFMAs on random operands under the board's power cap (other.power_ceiling.mfma_only_tflops)"
                                                        if out["roofline"].get("bound") == "mfma" else "read-only HBM stream (other.hbm_ceiling.read_stream_gbs)")
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             # after the timed region and after the ranks have parted: the oracle on this workload's per-rank shape, host cores only
             keys = min(w["ctx"], 32768) if w["mode"] == "dynamic" else w["ctx"] - math.ceil(w["ctx"] / (1 + w["pd"]))
             try:

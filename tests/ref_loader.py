@@ -1,8 +1,8 @@
 """Loads the REFERENCE's own attention wrapper and cache engine (sarathi-lean) against the MI355X drop-ins.  TEST INFRASTRUCTURE.
 
-Source: the files in place under /root/reference when it exists (this container), else their byte-compiled form under
-oracle/_ref/pyref (oracle/build_pyref.py; what travels to the GPU box).  The rest of sarathi's import closure (config, logger,
-metrics, ray ...) is replaced by inert stubs; `vattention`, `flash_attn` and `sarathi.cache_ops` resolve to the drop-ins
+Source: their byte-compiled form under oracle/_ref/pyref, which build() makes (oracle/build_pyref.py), so that no test reads
+outside the repository; before a build, the files in place in the reference tree (VATTN_REFERENCE_DIR).  The rest of sarathi's
+import closure (config, logger, metrics, ray ...) is replaced by inert stubs; `vattention`, `flash_attn` and `sarathi.cache_ops` resolve to the drop-ins
 (vattention_amd/dropin.py) — so every line of the reference's forward() / step() executes unmodified on the native stack.
 """
 import importlib.machinery
@@ -29,11 +29,11 @@ MODNAME = {
 
 
 def available() -> str:
-    """'source', 'pyc' or '' (neither present)."""
-    if all(os.path.exists(os.path.join(REF, p)) for p in SRC.values()):
-        return "source"
+    """'pyc', 'source' or '' (neither present)."""
     if all(os.path.exists(os.path.join(ROOT, "oracle", "_ref", "pyref", n + ".pyc")) for n in SRC):
         return "pyc"
+    if all(os.path.exists(os.path.join(REF, p)) for p in SRC.values()):
+        return "source"
     return ""
 
 

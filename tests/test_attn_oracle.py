@@ -168,9 +168,11 @@ def test_rotary_oracle_matches_scalar_half_arithmetic_and_is_a_rotation():
 def _intree_cases():
     import os
     import numpy as np
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attn_intree_ref_mha.npz")
-    z = np.load(path)
-    return z, sorted({k.split("/")[0] for k in z.files})
+    z = {}
+    for f in ("attn_intree_ref_mha.npz", "attn_intree_ref_mha_ops.npz"):      # plain cases, operator-by-composition cases
+        with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f)) as part:
+            z.update({k: part[k] for k in part.files})
+    return z, sorted({k.split("/")[0] for k in z})
 
 
 def _op_case(name):

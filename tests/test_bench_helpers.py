@@ -148,3 +148,42 @@ def test_power_ceiling_leg_reports_ratios_and_never_raises(monkeypatch, tmp_path
     assert "not built" in bench.power_ceiling(1000.0)["error"]
     pc, hc = bench.measured_ceilings(1000.0, 5000.0)
     assert "error" in pc and "error" in hc
+
+
+def test_output_tap_samples_what_the_callers_receive_and_keeps_the_budget(tmp_path):
+    """--dump-outputs: at most OutputTap.ROWS evenly spaced rows of every iteration's output, in issue order, with (iteration, row) beside
+    them; over the byte budget a seeded subset of the rows is written, the same one every time."""
+    import numpy as np
+
+    class Runner:
+        stream = None
+
+        def __init__(self):
+            self.n = 0
+
+        def run_iteration(self, mds):
+            self.n += 1
+            T = mds
+            return (torch.arange(T * 8, dtype=torch.float16).view(T, 8) + 1000 * self.n).clone()
+
+    r = Runner()
+    tap = bench.OutputTap(r)
+    got = [r.run_iteration(T) for T in (100, 3, 16)]
+    tap.close()
+    assert r.run_iteration.__func__ is Runner.run_iteration
+    tap.write(str(tmp_path))
+    out, rows = np.load(tmp_path / "attention_out.npy"), np.load(tmp_path / "attention_out_rows.npy")
+    assert out.dtype == np.float32 and rows.dtype == np.float64 and out.shape == (16 + 3 + 16, 8) and rows.shape == (35, 2)
+    assert rows[:16, 1].tolist() == [6.0 * j for j in range(16)] and rows[16:19].tolist() == [[1, 0], [1, 1], [1, 2]]
+    for (it, row), o in zip(rows.astype(int), out):
+        assert np.array_equal(o, got[it][row].float().numpy())
+    subsets = []
+    for _ in range(2):
+        tap = bench.OutputTap(r)
+        for T in (100, 3, 16):
+            r.run_iteration(T)
+        tap.close()
+        tap.write(str(tmp_path), "_small", budget=10 * (8 * 4 + 16))
+        subsets.append(np.load(tmp_path / "attention_out_rows_small.npy"))
+    assert subsets[0].shape == (10, 2) and np.array_equal(subsets[0], subsets[1])
+    assert np.load(tmp_path / "attention_out_small.npy").nbytes + subsets[0].nbytes <= 10 * (8 * 4 + 16)

@@ -1,48 +1,15 @@
-"""Where /root/reference is present (build container): the reference's OWN fa_vattn wrapper and cache-engine source
-files import against the drop-ins (vattention / flash_attn / sarathi.cache_ops) with inert stubs for the rest of
-sarathi's import closure, and bind to the MI355X-native symbols.  Nothing is copied; the files are loaded in place."""
-import importlib.util
-import os
-import sys
-import types
-
+"""The reference's OWN fa_vattn wrapper and cache-engine files import against the drop-ins (vattention / flash_attn /
+sarathi.cache_ops) with inert stubs for the rest of sarathi's import closure, and bind to the MI355X-native symbols.  The files
+are loaded as build() left them under oracle/_ref/pyref (tests/ref_loader.py); nothing is copied."""
 import pytest
 
-REF = os.environ.get("VATTN_REFERENCE_DIR", "/root/reference")
-WRAP = os.path.join(REF, "sarathi-lean/sarathi/model_executor/attention/vattention_flashattention_wrapper.py")
+from tests import ref_loader
 
 
-@pytest.mark.skipif(not os.path.exists(WRAP), reason="reference tree not present")
+@pytest.mark.skipif(not ref_loader.available(), reason="reference wrapper/engine not built (oracle/_ref/pyref)")
 def test_reference_wrapper_imports_against_dropins():
-    saved = dict(sys.modules)
-    try:
-        import vattention_amd.dropin as dropin
-        for name in ("vattention", "flash_attn", "sarathi", "sarathi.cache_ops"):
-            sys.modules.pop(name, None)
-        dropin.install(force=True)
-
-        def stub(name, **attrs):
-            m = types.ModuleType(name)
-            m.__dict__.update(attrs)
-            sys.modules[name] = m
-            return m
-        stub("sarathi.config", ModelConfig=object, ParallelConfig=object, CacheConfig=object)
-        stub("sarathi.core"); stub("sarathi.core.datatypes")
-        stub("sarathi.core.datatypes.sequence", SequenceMetadata=object, Sequence=object)
-        stub("sarathi.logger", init_logger=lambda n: __import__("logging").getLogger(n))
-        stub("sarathi.metrics")
-        from vattention_amd.attention.timers import OperationMetrics, OpTimer
-        stub("sarathi.metrics.constants", OperationMetrics=OperationMetrics)
-        stub("sarathi.metrics.cuda_timer", CudaTimer=OpTimer)
-        stub("sarathi.model_executor"); stub("sarathi.model_executor.attention")
-        base_path = os.path.join(os.path.dirname(WRAP), "base_attention_wrapper.py")
-        spec = importlib.util.spec_from_file_location("sarathi.model_executor.attention.base_attention_wrapper", base_path)
-        base = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = base
-        spec.loader.exec_module(base)
-        spec = importlib.util.spec_from_file_location("ref_vattn_fa_wrapper", WRAP)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
+    with ref_loader.loaded() as ref:
+        mod = ref.wrapper_mod
         import vattention_amd.cache_ops as co
         import vattention_amd.flash_attn as fa
         import vattention_amd.vattention as va
@@ -57,9 +24,6 @@ def test_reference_wrapper_imports_against_dropins():
                    "show_kvcache_config", "show_allocator_state", "step", "map_common_pages", "step_async",
                    "alloc_new_batch_idx", "free_batch_idx", "num_free_kvblocks"):
             assert callable(getattr(va, fn))
-    finally:
-        sys.modules.clear()
-        sys.modules.update(saved)
 
 
 def test_backend_registry_resolves_native_and_hybrid_backends():
