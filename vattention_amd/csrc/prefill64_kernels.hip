@@ -28,7 +28,7 @@
 namespace vattn_k {
 
 
-// The schedule of the tile step (compile-time constants below): 24 of the tile's 32 exp2 pairs start in phase A, a fragment ring of 4
+// The schedule of the tile step (tile_step in prefill64_common.h; its compile-time constants below): 24 of the tile's 32 exp2 pairs start in phase A, a fragment ring of 4
 // (three fragments ahead of their MFMA), the row-max chain in phase-B groups 8-23, the per-tile wait + barrier in front of group 8, one
 // LDS-DMA piece in groups 9, 12, ... 30.  Every alternative that was measured — other placements, the XOR-swizzled K image, timing
 // ablations, per-group clock stamps, the issue-price list of round 6 — lives in the LAB copy of this kernel, tools/lab/csrc/prefill64_lab.hip
@@ -53,20 +53,6 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     extern __shared__ __attribute__((aligned(16))) char smem[];      // K ring [2][16 KiB], then V ring [3][16 KiB]; LDS address 0
     // (no static __shared__ in this kernel: the LDS-DMA destinations are ABSOLUTE LDS addresses that assume smem starts at 0; the
     // merge ticket lives in the 16 bytes behind the V ring)
-    // The K image in LDS is stored as 16 pieces of 4 rows, each piece 1088 bytes apart (64
-    // bytes of padding), inside a piece chunk c of row r3 at byte 64*c + 16*r3.  ds_read_b128's lane groups ({0-3,12-15,20-27}, ...)
-    // then hit 16 distinct 16-byte slots of the 256-byte bank row WITHOUT an XOR swizzle, so the address of fragment (kk, kb) is
-    // one lane-dependent register + the immediate 8704*kb + 128*kk (+ the slot, static because slots go by (t - tb) & 1 and the
-    // loop is unrolled twice): no per-fragment address arithmetic in the hot loop.
-    constexpr int KPIECE = 1088;
-    constexpr int KSLOT = 16 * 1088;
-    constexpr int VBASE = 36864;
-    // MS: first phase-B group of the row-max chain of S'(t+1).  BJ: the phase-B group that opens with the per-tile wait + barrier; the
-    // eight DMA pieces go out in groups D0, D0 + DS, ... (all >= BJ).
-    static_assert(D0 >= BJ && D0 + 7 * DS < 32, "DMA pieces behind the barrier, inside phase B");
-    static_assert(NA >= 16 && NA < 32, "key slice 0 of P is packed in phase-A groups 13 / 15: its eight pairs must be exponentiated by group 12");
-    static_assert(MS >= 4 && MS + 19 < 32, "row-max chain >= 4 MFMAs behind the last S^T MFMA, its reduction inside phase B");
-    auto dma_gap = [](int k) { return D0 + DS * k; };
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -129,9 +115,8 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
         const int key = 16 * j + (lane >> 2);
         voff[j] = (unsigned)key * v_rs_bytes + (unsigned)((4 * wave + (lane & 3)) << 4);
     }
-    using M = Mfma<T>;
-    const unsigned k_lds_wave = (unsigned)(wave * 4 * KPIECE);                 // this wave's four K pieces inside a K slot
-    const unsigned v_lds_wave = (unsigned)(VBASE + wave * 4096);               // ... and V pieces inside a V slot
+    const unsigned k_lds_wave = (unsigned)(wave * 4 * kKPiece);                 // this wave's four K pieces inside a K slot
+    const unsigned v_lds_wave = (unsigned)(kVBase + wave * 4096);               // ... and V pieces inside a V slot
     auto kslot = [&](int t) { return (t - tb) & 1; };                          // K(t)'s slot of the ring
     auto k_rsrc = [&](int t) -> u32x4 {
         int rem = Lk - t * PF_BN;
@@ -145,11 +130,11 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     };
     auto dma_k_all = [&](int t) {      // K(t) -> K slot t & 1, this wave's four pieces
         const u32x4 r = k_rsrc(t);
-        const unsigned l0 = k_lds_wave + (unsigned)(kslot(t) * KSLOT);
+        const unsigned l0 = k_lds_wave + (unsigned)(kslot(t) * kKSlot);
         dma_piece_first(l0, r, koff[0]);
-        dma_piece(l0 + KPIECE, r, koff[1]);
-        dma_piece(l0 + 2 * KPIECE, r, koff[2]);
-        dma_piece(l0 + 3 * KPIECE, r, koff[3]);
+        dma_piece(l0 + kKPiece, r, koff[1]);
+        dma_piece(l0 + 2 * kKPiece, r, koff[2]);
+        dma_piece(l0 + 3 * kKPiece, r, koff[3]);
     };
     auto dma_v_all = [&](int t) {
         const u32x4 r = v_rsrc(t);
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     if (nt * PF_BN > Lk) {
         const uint4 z = make_uint4(0, 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < (3 * S::kTileBytes) / (256 * 16); i++) *(uint4*)(smem + VBASE + (i * 256 + tid) * 16) = z;
+        for (int i = 0; i < (3 * S::kTileBytes) / (256 * 16); i++) *(uint4*)(smem + kVBase + (i * 256 + tid) * 16) = z;
         __syncthreads();
     }
     // (asking for V(tb) and K(tb+1) only once Q sits in its registers — so that the wait for Q does not also wait for them — was measured:
@@ -232,20 +217,9 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     }
 
     // LDS fragment addressing: one lane-dependent base per tensor + immediate offsets
-    const unsigned kfrag_lane = (unsigned)((l31 >> 2) * KPIECE + (l31 & 3) * 16 + g * 64);
-    auto kfrag = [&](const char* ksm, int f) -> V8 {                  // f = 2*kk + kb: K rows 32*kb + l31, d = 16*kk + 8*g ..
-        const int kk = f >> 1, kb = f & 1;
-        return *(const V8*)(ksm + kb * 8 * KPIECE + kk * 128 + kfrag_lane);
-    };
+    const unsigned kfrag_lane = (unsigned)((l31 >> 2) * kKPiece + (l31 & 3) * 16 + g * 64);
     const int i16 = lane & 15, dh = (lane >> 4) & 1;
     const unsigned vfrag_lane = (unsigned)((4 * g + (i16 >> 2)) * 64 + (16 * dh + 4 * (i16 & 3)) * 2);
-    auto vfrag = [&](const char* vsm, int f) -> V8 {                  // f = 4*ks + db: keys 16*ks .. 16*ks+15, d block db
-        const int ks = f >> 2, db = f & 3;
-        const char* a1 = vsm + db * S::kVSubBytes + (16 * ks) * 64 + vfrag_lane;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1 + 8 * 64));
-        return join_tr<V8>(lo, hi);
-    };
     // masks tile tt's scores in place (ragged end of the sequence / causal diagonal) — wave-uniform decision by the caller
     auto mask_tile = [&](int tt, f32x16 (&s)[2][2]) {
         const int n0 = tt * PF_BN;
@@ -266,31 +240,6 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     // 64 tt + 64 > Lk  <=>  tt >= Lk >> 6;   64 tt + 63 > qw0 + off  <=>  tt >= ((qw0 + off - 63) >> 6) + 1 (arithmetic shift)
     const int t_mask = min(Lk >> 6, causal ? ((qw0 + off - 63) >> 6) + 1 : 0x7fffffff);
     auto needs_mask = [&](int tt) -> bool { return tt >= t_mask; };
-    auto row_max = [&](const f32x16 (&s)[2][2], int qc) -> float {
-        float m0 = fmaxf(s[0][qc][0], s[1][qc][0]);
-#pragma unroll
-        for (int r = 1; r < 16; r++) m0 = fmaxf(fmaxf(m0, s[0][qc][r]), s[1][qc][r]);     // v_max3_f32
-        return fmaxf(m0, swap_halves(m0));
-    };
-    // moves the running maximum of query block qc up by delta >= 0 (log2 units, per lane): everything accumulated at the old scale
-    // — O and l — is rescaled exactly once (cdna guide T13); scores not yet exponentiated are raw and take the new maximum
-    auto raise_max = [&](int qc, float delta) {
-        const float alpha = fast_exp2(-delta);
-        nmsub[qc] -= delta;
-#pragma unroll
-        for (int i = 0; i < DB; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) o[i][qc][r] *= alpha;
-#pragma unroll
-        for (int a4 = 0; a4 < 2; a4++) l_acc[qc][a4] *= alpha;
-    };
-    // P(t) -> the PV B-operand fragment of key slice ks for query block qc: slot (g, j) <-> P registers 8*(ks&1) + j of key block ks>>1
-    auto pack_p = [&](const f32x16 (&pt)[2][2], int ks, int qc) -> V8 {
-        V8 r;
-#pragma unroll
-        for (int j = 0; j < 8; j++) r[j] = X::cvt(pt[ks >> 1][qc][8 * (ks & 1) + j]);
-        return r;
-    };
 
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // this wave's pieces of K(tb) landed; V(tb), K(tb+1) may still fly
     __builtin_amdgcn_s_barrier();
@@ -298,18 +247,7 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     f32x16 sc[2][2];      // S(t): raw scores of the current tile; becomes P(t) in place
     f32x16 sd[2][2];
     {
-        const char* ksm = smem + kslot(tb) * KSLOT;
-#pragma unroll
-        for (int f = 0; f < 2 * KK; f++) {
-            const V8 a = kfrag(ksm, f);
-#pragma unroll
-            for (int qc = 0; qc < 2; qc++) {
-                if (f < 2) M::qk_first(sc[f & 1][qc], a, qf[qc][f >> 1]);
-                else M::qk_acc(sc[f & 1][qc], a, qf[qc][f >> 1]);
-            }
-        }
-        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");     // the last MFMA results are VALU-readable from here
-        SCHED_FENCE();
+        first_scores<T>(smem + kslot(tb) * kKSlot, sc, qf, kfrag_lane);
         if (needs_mask(tb)) mask_tile(tb, sc);
 #pragma unroll
         for (int qc = 0; qc < 2; qc++) {
@@ -318,154 +256,26 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
         }
     }
 
-    // ---- software pipeline of the softmax VALU work, in units of PAIRS of scores (pair e: key block e>>4, half (e>>3)&1, query
-    // block (e>>2)&1, registers 8*half + 2*(e&3), +1 — the order in which the P.V key slices consume them).  Stage E (two
-    // v_exp) of pair e sits in group GE(e) of the tile's 64 MFMA groups, stage M (two v_fma: s*scale*log2e - m*scale*log2e) one
-    // group earlier, stage A (two v_add into the two row-sum accumulators) one group later: no instruction waits for the one
-    // before it (one wave per SIMD: a stalled wave issues no MFMA either).
-    auto GE = [](int e) { return e < NA ? 1 + (e * 30) / NA : 33 + ((e - NA) * 17) / (32 - NA); };
-#define P64_X0(cur, e) cur[(e) >> 4][((e) >> 2) & 1][8 * (((e) >> 3) & 1) + 2 * ((e) & 3)]
-#define P64_X1(cur, e) cur[(e) >> 4][((e) >> 2) & 1][8 * (((e) >> 3) & 1) + 2 * ((e) & 3) + 1]
     // the scale as a REAL scalar register: the compiler satisfies "s"(a float the VALU computed) with a vector register, and the fma then
     // read three vector registers beside a running MFMA (and cost copies)
     const unsigned escale_s = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, escale));
-    auto softmax_stages = [&](int G, f32x16 (&cur)[2][2]) {
-#pragma unroll
-        for (int e = 0; e < 32; e++) {
-            const int qc = (e >> 2) & 1;
-            if (GE(e) - 1 == G)
-                asm("v_fma_f32 %0, %0, %2, %3\n\tv_fma_f32 %1, %1, %2, %3" : "+v"(P64_X0(cur, e)), "+v"(P64_X1(cur, e)) : "s"(escale_s), "v"(nmsub[qc]));
-            if (GE(e) == G) asm("v_exp_f32 %0, %0\n\tv_exp_f32 %1, %1" : "+v"(P64_X0(cur, e)), "+v"(P64_X1(cur, e)));
-            if (GE(e) + 1 == G)      // (v_pk_add_f32: a packed-f32 instruction beside the MFMAs costs 43 cycles, six plain ones)
-                asm("v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3" : "+v"(l_acc[qc][0]), "+v"(l_acc[qc][1]) : "v"(P64_X0(cur, e)), "v"(P64_X1(cur, e)));
-        }
-    };
 
-    // ---- the DMA stream's scalars, carried across the tile steps and advanced INSIDE MFMA gaps: a lone wave pays an issue slot for
-    // every SALU instruction, and whatever sits between the last MFMA of a step and the first of the next is not hidden at all ----
-    // rk / rv: descriptors of K(t+2) / V(t+1) at step entry (base, bytes left from the base on); phase B moves them one tile on and
-    // fetches K(t+3) / V(t+2) through them
+    // ---- the DMA stream's scalars (tile_step, prefill64_common.h) ----
+    // rk / rv: descriptors of K(t+2) / V(t+1) at step entry (base, bytes left from the base on)
     const unsigned k_tile_b = (unsigned)PF_BN * k_rs_bytes, v_tile_b = (unsigned)PF_BN * v_rs_bytes;
     int k_rows_left = Lk - (tb + 2) * PF_BN, v_rows_left = Lk - (tb + 1) * PF_BN;      // rows of the sequence behind the descriptor's base
-    auto bound = [](int rows, unsigned rs) -> unsigned {      // scalar min / max: the compiler's own clamp is a VALU v_med3 (+ a copy back that it cannot do)
-        int r;
-        asm("s_min_i32 %0, %1, 64\n\ts_max_i32 %0, %0, 0" : "=s"(r) : "s"(rows) : "scc");
-        return (unsigned)r * rs;
-    };
     const unsigned long long kp0 = (unsigned long long)kbase + (unsigned long long)(tb + 2) * k_tile_b;
     const unsigned long long vp0 = (unsigned long long)vbase + (unsigned long long)(tb + 1) * v_tile_b;
     u32x4 rk = {(unsigned)kp0, (unsigned)(kp0 >> 32) & 0xffffu, bound(k_rows_left, k_rs_bytes), 0x00020000u};
     u32x4 rv = {(unsigned)vp0, (unsigned)(vp0 >> 32) & 0xffffu, bound(v_rows_left, v_rs_bytes), 0x00020000u};
     // byte offsets inside the V ring of V(t)'s slot and of the slot V(t+2) goes to (= the one V(t-1) left): slots go by (t - tb) % 3
     unsigned vs_cur = 0, vs_dma = 2 * S::kTileBytes;
-    // One tile step of the wave.  cur holds S(t) on entry and P(t) afterwards, nxt receives S(t+1); kf0 / kf1 hold the first two
-    // K(t+1) fragments on entry (read before the previous step ended) and the first two of K(t+2) on exit.
-    // Invariants at entry: K(t+1) and V(t) have landed and every wave knows it (the barrier of step t-1); K(t+2) and V(t+1) are
-    // in flight.  The barrier of this step opens phase-B group BJ: by then every wave has finished reading K(t+1) (phase A) and V(t-1)
-    // (step t-1), so K(t+3) -> slot of K(t+1) and V(t+2) -> slot of V(t-1) may be issued behind it — one piece every DS-th group from
-    // group D0 on (back-to-back pieces in the barrier's own group and the seven after it, round 2's placement, measured 1-2 % slower on
-    // boxes that are not pinned at their power limit: profiles/r03_p64_schedules.txt).
+    // One tile step of the wave: the 64 groups of tile_step, then the masking of S'(t+1) and the deferred rescale.
     auto step = [&](int t, const int par, f32x16 (&cur)[2][2], f32x16 (&nxt)[2][2], V8& kf0, V8& kf1, V8& kf2) {
-        // par = (t - tb) & 1, a literal at both call sites: with the padded K layout every K fragment address folds to lane + immediate
-        const int s_cur = par;                                                  // slot of K(t), K(t+2)
-        const char* ksm = smem + (s_cur ^ 1) * KSLOT;                           // K(t+1)
-        const char* ksm_next = smem + s_cur * KSLOT;                            // K(t+2)
-        const char* vsm = smem + VBASE + vs_cur;                                // V(t)
-        const unsigned lk0 = k_lds_wave + (unsigned)((s_cur ^ 1) * KSLOT);      // K(t+3) -> the slot K(t+1) leaves
-        unsigned lv0 = 0;                                                       // V(t+2)'s pieces of this wave (set in phase B)
-        const bool mask_next = needs_mask(t + 1);                               // ragged end / causal diagonal: wave-uniform, the last tiles only
-        // Every wave runs the SAME straight-line body for every tile of the workgroup (the barrier makes the waves wait for each other
-        // anyway): a tile that lies wholly beyond a wave's causal limit is masked to -inf, contributes P = 0, and leaves the running
-        // maximum alone; past the last tile S'(t+1) is computed from a zero-filled K slot and never used.
-        // ---------------- 64 groups of { MFMA ; fragment read ahead ; a slice of softmax VALU } ----------------
-        // phase A: S'(t+1) = K(t+1).Q^T - m   (32 MFMAs: k-step kk = i>>2, key block (i>>1)&1, query block i&1)
-        V8 pf[2][2];         // P(t) fragments of the key slice being multiplied and of the next one
-        V8 kf[RING];         // RING - 1 fragments (twice as many MFMAs) ahead of their use
-        V8 vf[RING];         // V(t)^T fragments of phase B
-        SCHED_FENCE();
-#pragma unroll
-        for (int i = 0; i < 32; i++) {
-            const int f = i >> 1, qc = i & 1;
-            if (f < RING - 1) {
-                // the fragments read before the previous step ended sit in accumulator registers
-                const V8 a = f == 0 ? kf0 : (f == 1 ? kf1 : kf2);
-                if (i < 4) M::qk_first_a(nxt[f & 1][qc], a, qf[qc][f >> 1]);
-                else M::qk_acc_a(nxt[f & 1][qc], a, qf[qc][f >> 1]);
-            } else if (i < 4) M::qk_first(nxt[f & 1][qc], kf[f % RING], qf[qc][f >> 1]);
-            else M::qk_acc(nxt[f & 1][qc], kf[f % RING], qf[qc][f >> 1]);
-            if ((i & 1) == 0 && f + RING - 1 < 2 * KK) kf[(f + RING - 1) % RING] = kfrag(ksm, f + RING - 1);
-            softmax_stages(i, cur);
-            // key slice 0 of P(t) (pairs 0-7: exponentiated by group GE(7) <= 12 for NA >= 16) is packed HERE, so the first P.V MFMA
-            // of phase B does not wait for eight conversions issued right in front of it
-            if (i == 13) pf[0][0] = pack_p(cur, 0, 0);
-            if (i == 15) pf[0][1] = pack_p(cur, 0, 1);
-            // the DMA stream's scalars move one tile on (SALU work, inside gaps)
-            if (i == 17) lv0 = v_lds_wave + vs_dma;
-            if (i == 19) asm volatile("s_mov_b32 %1, %0\n\ts_add_u32 %0, %0, %2\n\ts_cmp_eq_u32 %0, %3\n\ts_cselect_b32 %0, 0, %0"
-                                      : "+s"(vs_cur), "=&s"(vs_dma) : "i"(S::kTileBytes), "i"(3 * S::kTileBytes) : "scc");
-            if (i == 21) k_rsrc_advance(rk, k_rows_left, k_tile_b, k_rs_bytes);
-            if (i == 23) v_rsrc_advance(rv, v_rows_left, v_tile_b, v_rs_bytes);
-            // V(t) landed a step ago: its first fragments are asked for while the last S' MFMAs run (the K ring has stopped reading at i = 24)
-            if (i == 26) vf[0] = vfrag(vsm, 0);
-            if (i == 28) vf[1] = vfrag(vsm, 1);
-            if (i == 30 && RING > 3) vf[2] = vfrag(vsm, 2);
-            SCHED_FENCE();
-        }
-        // phase B: O^T += V(t)^T.P(t)^T   (32 MFMAs: key slice ks = j>>3, d block (j>>1)&3, query block j&1)
-        float mx0 = -INFINITY, mx1 = -INFINITY, g0 = -INFINITY, g1 = -INFINITY, grow = -INFINITY;
-        SCHED_FENCE();
-#pragma unroll
-        for (int j = 0; j < 32; j++) {
-            const int f = j >> 1, ks = j >> 3, qc = j & 1;
-            if (j == BJ) {
-                // this wave's pieces of K(t+2) and V(t+1) (issued one step ago) have landed; behind the barrier everyone's have, and
-                // every wave is past its reads of K(t+1) and V(t-1)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            // (a P fragment is packed at least one MFMA group before its first use: no VALU -> MFMA operand hazard to pad)
-            M::pv(o[f & 3][qc], vf[f % RING], pf[ks & 1][qc]);
-            if ((j & 1) == 0 && f + RING - 1 < 16) vf[(f + RING - 1) % RING] = vfrag(vsm, f + RING - 1);
-            softmax_stages(32 + j, cur);
-            // P fragments of key slice ks+1 are packed while slice ks is multiplied (4 cvt_pk per group, groups 4 and 6 of a slice)
-            if (ks < 3 && (j & 7) == 4) pf[(ks + 1) & 1][0] = pack_p(cur, ks + 1, 0);
-            if (ks < 3 && (j & 7) == 6) pf[(ks + 1) & 1][1] = pack_p(cur, ks + 1, 1);
-            // row max of S'(t+1): 2 chains x 16 v_max3, groups MS .. MS+15 (>= 4 MFMAs after the last S^T MFMA was issued); the
-            // half-wave exchange and the growth test follow in the next gaps, so that only the branch itself is left behind the
-            // step's last MFMA
-            if (j >= MS && j < MS + 16) {
-                const int r = j - MS;
-                if (r == 0) {      // the chain's first link needs no -inf to start from
-                    asm("v_max_f32_e32 %0, %1, %2" : "=v"(mx0) : "v"(nxt[0][0][0]), "v"(nxt[1][0][0]));
-                    asm("v_max_f32_e32 %0, %1, %2" : "=v"(mx1) : "v"(nxt[0][1][0]), "v"(nxt[1][1][0]));
-                } else {
-                    asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mx0) : "v"(nxt[0][0][r]), "v"(nxt[1][0][r]));
-                    asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mx1) : "v"(nxt[0][1][r]), "v"(nxt[1][1][r]));
-                }
-            }
-            if (j == MS + 16) mx0 = max_halves(mx0);
-            if (j == MS + 17) mx1 = max_halves(mx1);
-            if (j == MS + 18) {
-                // growth of the row maxima over the running maxima, log2 units (nmsub = -m*scale*log2e; -inf for rows that see nothing here)
-                asm("v_fma_f32 %0, %2, %4, %5\n\tv_fma_f32 %1, %3, %4, %6" : "=&v"(g0), "=&v"(g1) : "v"(mx0), "v"(mx1), "s"(escale_s), "v"(nmsub[0]), "v"(nmsub[1]));
-            }
-            if (j == MS + 19) asm("v_max_f32 %0, %1, %2" : "=v"(grow) : "v"(g0), "v"(g1));
-            // this wave's four pieces of K(t+3) and of V(t+2): every piece takes piece 0's per-lane offset, its distance from piece 0 (4 K rows |
-            // 16 V keys per piece) travels in the load's scalar offset (prefill64_common.h)
-            if (j == dma_gap(0)) dma_piece_at<0>(lk0, rk, koff[0]);
-            if (j == dma_gap(1)) dma_piece_so<KPIECE, 4>(lk0, rk, koff[0], k_rs_bytes);
-            if (j == dma_gap(2)) dma_piece_so<2 * KPIECE, 8>(lk0, rk, koff[0], k_rs_bytes);
-            if (j == dma_gap(3)) dma_piece_so<3 * KPIECE, 12>(lk0, rk, koff[0], k_rs_bytes);
-            if (j == dma_gap(4)) dma_piece_at<0>(lv0, rv, voff[0]);
-            if (j == dma_gap(5)) dma_piece_so<1024, 16>(lv0, rv, voff[0], v_rs_bytes);
-            if (j == dma_gap(6)) dma_piece_so<2048, 32>(lv0, rv, voff[0], v_rs_bytes);
-            if (j == dma_gap(7)) dma_piece_so<3072, 48>(lv0, rv, voff[0], v_rs_bytes);
-            if (j == 27) kf0 = kfrag(ksm_next, 0);          // the next step's first K fragments: K(t+2) is behind the barrier
-            if (j == 28) kf1 = kfrag(ksm_next, 1);
-            if (j == 29 && RING > 3) kf2 = kfrag(ksm_next, 2);
-            SCHED_FENCE();
-        }
-        if (mask_next) {
+        auto [mx0, mx1, g0, g1, grow] = tile_step<T, NA, RING, MS, BJ, D0, DS>(par, smem, cur, nxt, kf0, kf1, kf2, qf, o, l_acc, nmsub, rk, rv, k_rows_left,
+                                                                               v_rows_left, vs_cur, vs_dma, k_lds_wave, v_lds_wave, koff[0], voff[0], k_rs_bytes,
+                                                                               v_rs_bytes, k_tile_b, v_tile_b, kfrag_lane, vfrag_lane, escale_s, [](int) {});
+        if (needs_mask(t + 1)) {      // ragged end / causal diagonal: wave-uniform, the last tiles only
             mask_tile(t + 1, nxt);
             mx0 = row_max(nxt, 0);
             mx1 = row_max(nxt, 1);
@@ -476,8 +286,8 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
         if (__builtin_amdgcn_ballot_w64(grow > kDeferLog2) != 0) {          // rare: a row's maximum grew by > 2^6
             asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");                        // every PV result has landed in O
             SCHED_FENCE();
-            raise_max(0, fmaxf(g0, 0.f));
-            raise_max(1, fmaxf(g1, 0.f));
+            raise_max(o, l_acc, nmsub, 0, fmaxf(g0, 0.f));
+            raise_max(o, l_acc, nmsub, 1, fmaxf(g1, 0.f));
             SCHED_FENCE();
             asm volatile("s_nop 3" ::: "memory");                                    // accvgpr writes -> next MFMA read
         }
@@ -487,21 +297,19 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
     __builtin_amdgcn_s_barrier();                    // also: every wave is done with K(tb) (the prologue's S')
     dma_k_all(tb + 2);
     dma_v_all(tb + 1);
-    V8 kfa = kfrag(smem + kslot(tb + 1) * KSLOT, 0), kfb = kfrag(smem + kslot(tb + 1) * KSLOT, 1), kfc = kfrag(smem + kslot(tb + 1) * KSLOT, 2);
+    const char* ksm1 = smem + kslot(tb + 1) * kKSlot;
+    V8 kfa = kfrag<V8>(ksm1, 0, kfrag_lane), kfb = kfrag<V8>(ksm1, 1, kfrag_lane), kfc = kfrag<V8>(ksm1, 2, kfrag_lane);
     for (int t = tb; t < nt; t += 2) {
         step(t, 0, sc, sd, kfa, kfb, kfc);
         if (t + 1 < nt) step(t + 1, 1, sd, sc, kfa, kfb, kfc);
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 7" ::: "memory");      // trailing DMA retired (nothing may land in LDS of
     SCHED_FENCE();                                                                // a later workgroup); last PV results readable
-#undef P64_X0
-#undef P64_X1
 
     // ---- epilogue: O^T[d = 32*db + 8*(r>>2) + 4*g + (r&3)][query] ----
     // (Staging the fp32 partials of a key-range piece through LDS so that every store instruction writes whole 512-byte rows instead of
     // 32 bytes of 32 rows was built and measured in round 3: no gain — the cost of the partials (no-store ablation: 5-19 % of the
     // tensor-parallel launches, profiles/r03_p64_prologue_epilogue.txt) is their volume, not their coalescing.)
-    const float sc_ln = p.softmax_scale;
 #pragma unroll
     for (int qc = 0; qc < 2; qc++) {
         const int my_q = qw0 + 32 * qc + l31;
@@ -569,7 +377,6 @@ __global__ __launch_bounds__(256, 1) void prefill64_kernel(vattn_attn_params p, 
             }
         }
     }
-    (void)sc_ln;
 }
 
 // host side: grid as prefill_kernels.hip's 1-D / 3-D orders with 256-row query blocks

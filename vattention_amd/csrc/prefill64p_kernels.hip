@@ -16,10 +16,10 @@
 //     accumulators, take the new piece's first row maxima as its reference.
 // A piece shorter than 3 tiles does not chain OUT (its re-base points would lie in its predecessor's steps); the piece after it starts
 // cold — the same prologue as prefill64_kernel's.  Fused RoPE is not taken here (the launch keeps prefill64_kernel for it).
-// The tile step itself — the 64 hand-placed groups { MFMA ; fragment read ahead ; softmax slice } — is prefill64_kernel's product
-// instantiation (padded K image, NA = 24, fragment ring of 4, barrier at group 8, DMA in groups 9, 12, .. 30), restated here with
-// the four hooks the stream needs: descriptor re-base, mask parameters of the tile being scored, exported row maxima, no max-growth
-// test across a piece boundary.
+// The tile step itself — the 64 hand-placed groups { MFMA ; fragment read ahead ; softmax slice } — is tile_step (prefill64_common.h)
+// with prefill64_kernel's product schedule (padded K image, NA = 24, fragment ring of 4, barrier at group 8, DMA in groups 9, 12, .. 30).
+// What the stream needs around it: the piece's counters moved in a phase-A gap (the step's hook), descriptor re-base, mask parameters
+// of the tile being scored, exported row maxima, no max-growth test across a piece boundary.
 #include "prefill64_common.h"
 
 namespace vattn_k {
@@ -44,13 +44,6 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
     constexpr int KK = HD / 16;
     constexpr int DB = HD / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];      // K ring, V ring (prefill64_kernel's map), 16 spare bytes, Q staging; LDS address 0
-    constexpr int KPIECE = 1088;
-    constexpr int KSLOT = 16 * 1088;
-    constexpr int VBASE = 36864;
-    static_assert(D0 >= BJ && D0 + 7 * DS < 32, "DMA pieces behind the barrier, inside phase B");
-    static_assert(NA >= 16 && NA < 32, "key slice 0 of P is packed in phase-A groups 13 / 15");
-    static_assert(MS >= 4 && MS + 19 < 32, "row-max chain inside phase B");
-    auto dma_gap = [](int k) { return D0 + DS * k; };
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -168,15 +161,14 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
         return x;
     };
 
-    // ---- DMA addressing (tile-invariant per-lane offsets; prefill64_kernel's padded K image and V sub-tiles) ----
+    // ---- DMA addressing (tile-invariant per-lane offsets; the padded K image and V sub-tiles of prefill64_common.h) ----
     // K piece pc = 4*wave + j holds rows 4*pc .. 4*pc+3 (lane i -> row 4*pc + (i & 3), chunk i >> 2); V piece j = (d block wave, keys 16*j ..):
     // lane i -> key 16*j + (i >> 2), global chunk 4*wave + (i & 3).  Piece j's offset = piece 0's + j x (4 K rows | 16 V keys).
     unsigned koff[1], voff[1];
     koff[0] = (unsigned)(16 * wave + (lane & 3)) * k_rs_bytes + (unsigned)((lane >> 2) << 4);
     voff[0] = (unsigned)(lane >> 2) * v_rs_bytes + (unsigned)((4 * wave + (lane & 3)) << 4);
-    using M = Mfma<T>;
-    const unsigned k_lds_wave = (unsigned)(wave * 4 * KPIECE);
-    const unsigned v_lds_wave = (unsigned)(VBASE + wave * 4096);
+    const unsigned k_lds_wave = (unsigned)(wave * 4 * kKPiece);
+    const unsigned v_lds_wave = (unsigned)(kVBase + wave * 4096);
     const unsigned q_lds_wave = (unsigned)(kQStage + wave * 16384);
     auto tile_desc = [&](unsigned long long base, int t, int Lk_, unsigned rs_bytes) -> u32x4 {
         int rem = Lk_ - t * PF_BN;
@@ -192,11 +184,11 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
     // cold start only: K(t) -> K slot `ks`, V(t) -> V slot `vs`
     auto dma_k_all = [&](int rec, int t, int ks) {
         const u32x4 r = tile_desc(PF64(rec, F_KB_LO), t, PF(rec, F_LK), k_rs_bytes);
-        const unsigned l0 = k_lds_wave + (unsigned)(ks * KSLOT);
+        const unsigned l0 = k_lds_wave + (unsigned)(ks * kKSlot);
         dma_piece_first(l0, r, koff[0]);
-        dma_piece(l0 + KPIECE, r, piece_off<4>(koff[0], k_rs_bytes));
-        dma_piece(l0 + 2 * KPIECE, r, piece_off<8>(koff[0], k_rs_bytes));
-        dma_piece(l0 + 3 * KPIECE, r, piece_off<12>(koff[0], k_rs_bytes));
+        dma_piece(l0 + kKPiece, r, piece_off<4>(koff[0], k_rs_bytes));
+        dma_piece(l0 + 2 * kKPiece, r, piece_off<8>(koff[0], k_rs_bytes));
+        dma_piece(l0 + 3 * kKPiece, r, piece_off<12>(koff[0], k_rs_bytes));
     };
     auto dma_v_all = [&](int rec, int t, int vs) {
         const u32x4 r = tile_desc(PF64(rec, F_VB_LO), t, PF(rec, F_LK), v_rs_bytes);
@@ -284,21 +276,10 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
             for (int a4 = 0; a4 < 2; a4++) l_acc[qc][a4] = 0.f;
     };
 
-    // LDS fragment addressing (prefill64_kernel's)
-    const unsigned kfrag_lane = (unsigned)((l31 >> 2) * KPIECE + (l31 & 3) * 16 + g * 64);
-    auto kfrag = [&](const char* ksm, int f) -> V8 {
-        const int kk = f >> 1, kb = f & 1;
-        return *(const V8*)(ksm + kb * 8 * KPIECE + kk * 128 + kfrag_lane);
-    };
+    // LDS fragment addressing (kfrag / vfrag, prefill64_common.h)
+    const unsigned kfrag_lane = (unsigned)((l31 >> 2) * kKPiece + (l31 & 3) * 16 + g * 64);
     const int i16 = lane & 15, dh = (lane >> 4) & 1;
     const unsigned vfrag_lane = (unsigned)((4 * g + (i16 >> 2)) * 64 + (16 * dh + 4 * (i16 & 3)) * 2);
-    auto vfrag = [&](const char* vsm, int f) -> V8 {
-        const int ks = f >> 2, db = f & 3;
-        const char* a1 = vsm + db * S::kVSubBytes + (16 * ks) * 64 + vfrag_lane;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1 + 8 * 64));
-        return join_tr<V8>(lo, hi);
-    };
     // masks tile tt of the piece whose (visible keys, first row of this wave + bottom-right offset) are (Lk_, qoff_)
     // kend_: one past the last key of the PIECE (64 x its last tile + 64): a piece shorter than three tiles is stepped over three anyway
     // (below), and the tiles behind its own — another share's keys, or nothing — must count for nothing
@@ -318,59 +299,18 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
                 }
         }
     };
-    auto row_max = [&](const f32x16 (&s)[2][2], int qc) -> float {
-        float m0 = fmaxf(s[0][qc][0], s[1][qc][0]);
-#pragma unroll
-        for (int r = 1; r < 16; r++) m0 = fmaxf(fmaxf(m0, s[0][qc][r]), s[1][qc][r]);
-        return fmaxf(m0, swap_halves(m0));
-    };
-    auto raise_max = [&](int qc, float delta) {
-        const float alpha = fast_exp2(-delta);
-        nmsub[qc] -= delta;
-#pragma unroll
-        for (int i = 0; i < DB; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) o[i][qc][r] *= alpha;
-#pragma unroll
-        for (int a4 = 0; a4 < 2; a4++) l_acc[qc][a4] *= alpha;
-    };
-    auto pack_p = [&](const f32x16 (&pt)[2][2], int ks, int qc) -> V8 {
-        V8 r;
-#pragma unroll
-        for (int j = 0; j < 8; j++) r[j] = X::cvt(pt[ks >> 1][qc][8 * (ks & 1) + j]);
-        return r;
-    };
 
     f32x16 sc[2][2];
     f32x16 sd[2][2];
 
-    auto GE = [](int e) { return e < NA ? 1 + (e * 30) / NA : 33 + ((e - NA) * 17) / (32 - NA); };
-#define P64_X0(cur, e) cur[(e) >> 4][((e) >> 2) & 1][8 * (((e) >> 3) & 1) + 2 * ((e) & 3)]
-#define P64_X1(cur, e) cur[(e) >> 4][((e) >> 2) & 1][8 * (((e) >> 3) & 1) + 2 * ((e) & 3) + 1]
-    // (round 6, as in prefill64_kernel: the scale in a REAL scalar register, the V^T fragments of phase B read in phase A's tail, the LDS-DMA
+    // (round 6, tile_step: the scale in a REAL scalar register, the V^T fragments of phase B read in phase A's tail, the LDS-DMA
     // pieces' distances in the loads' scalar offset, the row-max chain started from its first link: a VALU instruction beside the MFMAs costs
     // 7.3 cycles of this wave, a scalar one 0.3 — profiles/r06_p64_price_list.txt)
     const unsigned escale_s = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, escale));
-    auto softmax_stages = [&](int Gp, f32x16 (&cur)[2][2]) {
-#pragma unroll
-        for (int e = 0; e < 32; e++) {
-            const int qc = (e >> 2) & 1;
-            if (GE(e) - 1 == Gp)
-                asm("v_fma_f32 %0, %0, %2, %3\n\tv_fma_f32 %1, %1, %2, %3" : "+v"(P64_X0(cur, e)), "+v"(P64_X1(cur, e)) : "s"(escale_s), "v"(nmsub[qc]));
-            if (GE(e) == Gp) asm("v_exp_f32 %0, %0\n\tv_exp_f32 %1, %1" : "+v"(P64_X0(cur, e)), "+v"(P64_X1(cur, e)));
-            if (GE(e) + 1 == Gp)
-                asm("v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3" : "+v"(l_acc[qc][0]), "+v"(l_acc[qc][1]) : "v"(P64_X0(cur, e)), "v"(P64_X1(cur, e)));
-        }
-    };
 
-    // ---- the DMA stream's scalars (prefill64_kernel's; the descriptors live in s[92:95] / s[96:99]) ----
+    // ---- the DMA stream's scalars (tile_step's; the descriptors live in s[92:95] / s[96:99]) ----
     const unsigned k_tile_b = (unsigned)PF_BN * k_rs_bytes, v_tile_b = (unsigned)PF_BN * v_rs_bytes;
     int k_rows_left = 0, v_rows_left = 0;
-    auto bound = [](int rows, unsigned rs) -> unsigned {
-        int r;
-        asm("s_min_i32 %0, %1, 64\n\ts_max_i32 %0, %0, 0" : "=s"(r) : "s"(rows) : "scc");
-        return (unsigned)r * rs;
-    };
     u32x4 rk = {0u, 0u, 0u, 0x00020000u};
     u32x4 rv = {0u, 0u, 0u, 0x00020000u};
     // points the running descriptors at tile t of a piece (cold start: K(tb+2) / V(tb+1); re-base: the next piece's K(tb) / V(tb))
@@ -416,92 +356,19 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
     float bx0 = 0.f, bx1 = 0.f;                   // row maxima of the tile a seam scored (after masking)
     bool seam_now = false;                        // the step in flight scores the NEXT piece's first tile
 
-    // The step is prefill64_kernel's but for three things: the piece's counters move inside a gap, the row maxima of the tile scored are
+    // The step is tile_step plus three things: the piece's counters move inside a gap, the row maxima of the tile scored are
     // left where a seam can take them, and a seam's max-growth test is void.  The re-base of the K / V descriptors costs the step
     // nothing: the glue in front of a re-base step sets the descriptor to ONE TILE BEFORE the next piece's first tile, and the step's
     // ordinary one-tile move (groups 21 / 23) lands on it.
     auto step = [&](const int par, f32x16 (&cur)[2][2], f32x16 (&nxt)[2][2], V8& kf0, V8& kf1, V8& kf2) {
-        const int s_cur = par;
-        const char* ksm = smem + (s_cur ^ 1) * KSLOT;
-        const char* ksm_next = smem + s_cur * KSLOT;
-        const char* vsm = smem + VBASE + vs_cur;
-        const unsigned lk0 = k_lds_wave + (unsigned)((s_cur ^ 1) * KSLOT);
-        unsigned lv0 = 0;
-        V8 pf[2][2];
-        V8 kf[RING];
-        V8 vf[RING];
-        SCHED_FENCE();
-#pragma unroll
-        for (int i = 0; i < 32; i++) {
-            const int f = i >> 1, qc = i & 1;
-            if (f < RING - 1) {
-                const V8 a = f == 0 ? kf0 : (f == 1 ? kf1 : kf2);
-                if (i < 4) M::qk_first_a(nxt[f & 1][qc], a, qf[qc][f >> 1]);
-                else M::qk_acc_a(nxt[f & 1][qc], a, qf[qc][f >> 1]);
-            } else if (i < 4) M::qk_first(nxt[f & 1][qc], kf[f % RING], qf[qc][f >> 1]);
-            else M::qk_acc(nxt[f & 1][qc], kf[f % RING], qf[qc][f >> 1]);
-            if ((i & 1) == 0 && f + RING - 1 < 2 * KK) kf[(f + RING - 1) % RING] = kfrag(ksm, f + RING - 1);
-            softmax_stages(i, cur);
-            if (i == 13) pf[0][0] = pack_p(cur, 0, 0);
-            if (i == 15) pf[0][1] = pack_p(cur, 0, 1);
-            if (i == 17) lv0 = v_lds_wave + vs_dma;
-            if (i == 19) asm volatile("s_mov_b32 %1, %0\n\ts_add_u32 %0, %0, %2\n\ts_cmp_eq_u32 %0, %3\n\ts_cselect_b32 %0, 0, %0"
-                                      : "+s"(vs_cur), "=&s"(vs_dma) : "i"(S::kTileBytes), "i"(3 * S::kTileBytes) : "scc");
-            // (at a re-base point the descriptor was set back by one tile before the step: the same move lands on the next piece's first tile)
-            if (i == 21) k_rsrc_advance(rk, k_rows_left, k_tile_b, k_rs_bytes);
-            if (i == 23) v_rsrc_advance(rv, v_rows_left, v_tile_b, v_rs_bytes);
-            // the piece's counters move on inside a gap (pinned: scalar C++ would be sunk behind the step's last MFMA, where nothing
-            // hides it): t = the tile being scored, rem = tiles left after this step
+        // the piece's counters move on inside a gap of phase A (pinned: scalar C++ would be sunk behind the step's last MFMA, where
+        // nothing hides it): t = the tile being scored, rem = tiles left after this step
+        auto counters = [&](int i) {
             if (i == 25) asm volatile("s_add_u32 %0, %0, 1\n\ts_sub_u32 %1, %1, 1" : "+s"(t), "+s"(rem) : : "scc");
-            // V(t) landed a step ago: its first fragments are asked for while the last S' MFMAs run (the K ring has stopped reading at i = 24)
-            if (i == 26) vf[0] = vfrag(vsm, 0);
-            if (i == 28) vf[1] = vfrag(vsm, 1);
-            if (i == 30 && RING > 3) vf[2] = vfrag(vsm, 2);
-            SCHED_FENCE();
-        }
-        float mx0 = -INFINITY, mx1 = -INFINITY, g0 = -INFINITY, g1 = -INFINITY, grow = -INFINITY;
-        SCHED_FENCE();
-#pragma unroll
-        for (int j = 0; j < 32; j++) {
-            const int f = j >> 1, ks = j >> 3, qc = j & 1;
-            if (j == BJ) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            M::pv(o[f & 3][qc], vf[f % RING], pf[ks & 1][qc]);
-            if ((j & 1) == 0 && f + RING - 1 < 16) vf[(f + RING - 1) % RING] = vfrag(vsm, f + RING - 1);
-            softmax_stages(32 + j, cur);
-            if (ks < 3 && (j & 7) == 4) pf[(ks + 1) & 1][0] = pack_p(cur, ks + 1, 0);
-            if (ks < 3 && (j & 7) == 6) pf[(ks + 1) & 1][1] = pack_p(cur, ks + 1, 1);
-            if (j >= MS && j < MS + 16) {
-                const int r = j - MS;
-                if (r == 0) {
-                    asm("v_max_f32_e32 %0, %1, %2" : "=v"(mx0) : "v"(nxt[0][0][0]), "v"(nxt[1][0][0]));
-                    asm("v_max_f32_e32 %0, %1, %2" : "=v"(mx1) : "v"(nxt[0][1][0]), "v"(nxt[1][1][0]));
-                } else {
-                    asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mx0) : "v"(nxt[0][0][r]), "v"(nxt[1][0][r]));
-                    asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mx1) : "v"(nxt[0][1][r]), "v"(nxt[1][1][r]));
-                }
-            }
-            if (j == MS + 16) mx0 = max_halves(mx0);
-            if (j == MS + 17) mx1 = max_halves(mx1);
-            if (j == MS + 18) {
-                asm("v_fma_f32 %0, %2, %4, %5\n\tv_fma_f32 %1, %3, %4, %6" : "=&v"(g0), "=&v"(g1) : "v"(mx0), "v"(mx1), "s"(escale_s), "v"(nmsub[0]), "v"(nmsub[1]));
-            }
-            if (j == MS + 19) asm("v_max_f32 %0, %1, %2" : "=v"(grow) : "v"(g0), "v"(g1));
-            if (j == dma_gap(0)) dma_piece_at<0>(lk0, rk, koff[0]);
-            if (j == dma_gap(1)) dma_piece_so<KPIECE, 4>(lk0, rk, koff[0], k_rs_bytes);
-            if (j == dma_gap(2)) dma_piece_so<2 * KPIECE, 8>(lk0, rk, koff[0], k_rs_bytes);
-            if (j == dma_gap(3)) dma_piece_so<3 * KPIECE, 12>(lk0, rk, koff[0], k_rs_bytes);
-            if (j == dma_gap(4)) dma_piece_at<0>(lv0, rv, voff[0]);
-            if (j == dma_gap(5)) dma_piece_so<1024, 16>(lv0, rv, voff[0], v_rs_bytes);
-            if (j == dma_gap(6)) dma_piece_so<2048, 32>(lv0, rv, voff[0], v_rs_bytes);
-            if (j == dma_gap(7)) dma_piece_so<3072, 48>(lv0, rv, voff[0], v_rs_bytes);
-            if (j == 27) kf0 = kfrag(ksm_next, 0);
-            if (j == 28) kf1 = kfrag(ksm_next, 1);
-            if (j == 29 && RING > 3) kf2 = kfrag(ksm_next, 2);
-            SCHED_FENCE();
-        }
+        };
+        auto [mx0, mx1, g0, g1, grow] = tile_step<T, NA, RING, MS, BJ, D0, DS>(par, smem, cur, nxt, kf0, kf1, kf2, qf, o, l_acc, nmsub, rk, rv, k_rows_left,
+                                                                               v_rows_left, vs_cur, vs_dma, k_lds_wave, v_lds_wave, koff[0], voff[0], k_rs_bytes,
+                                                                               v_rs_bytes, k_tile_b, v_tile_b, kfrag_lane, vfrag_lane, escale_s, counters);
         // the tile just scored may need masking (at the seam the mask scalars are already the next piece's: VATTN_GLUE)
         if (__builtin_expect(t >= t_mask, 0)) {
             mask_tile(t, nxt, Lk_c, qoff_c, kend_c);
@@ -518,8 +385,8 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(grow > kDeferLog2) != 0, 0) && !seam_now) {      // (at the seam `grow` compares two pieces: void)
             asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
             SCHED_FENCE();
-            raise_max(0, fmaxf(g0, 0.f));
-            raise_max(1, fmaxf(g1, 0.f));
+            raise_max(o, l_acc, nmsub, 0, fmaxf(g0, 0.f));
+            raise_max(o, l_acc, nmsub, 1, fmaxf(g1, 0.f));
             SCHED_FENCE();
             asm volatile("s_nop 3" ::: "memory");
         }
@@ -598,7 +465,7 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
         }
         const uint4 z = make_uint4(0, 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < (3 * S::kTileBytes) / (256 * 16); i++) *(uint4*)(smem + VBASE + (i * 256 + tid) * 16) = z;
+        for (int i = 0; i < (3 * S::kTileBytes) / (256 * 16); i++) *(uint4*)(smem + kVBase + (i * 256 + tid) * 16) = z;
         __syncthreads();
     }
 
@@ -672,18 +539,7 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                  // this wave's pieces of K(tb) landed; V(tb), K(tb+1) may still fly
     __builtin_amdgcn_s_barrier();
     {
-        const char* ksm = smem;
-#pragma unroll
-        for (int f = 0; f < 2 * KK; f++) {
-            const V8 a = kfrag(ksm, f);
-#pragma unroll
-            for (int qc = 0; qc < 2; qc++) {
-                if (f < 2) M::qk_first(sc[f & 1][qc], a, qf[qc][f >> 1]);
-                else M::qk_acc(sc[f & 1][qc], a, qf[qc][f >> 1]);
-            }
-        }
-        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-        SCHED_FENCE();
+        first_scores<T>(smem, sc, qf, kfrag_lane);
         if (t >= t_mask) mask_tile(t, sc, Lk_c, qoff_c, kend_c);
 #pragma unroll
         for (int qc = 0; qc < 2; qc++) {
@@ -697,9 +553,9 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
     dma_v_all(cur, t + 1, 1);
     k_rebase(PF64(cur, F_KB_LO), t + 2, Lk_c);                        // the running descriptors at step entry: K(t+2), V(t+1)
     v_rebase(PF64(cur, F_VB_LO), t + 1, Lk_c);
-    kfa = kfrag(smem + KSLOT, 0);
-    kfb = kfrag(smem + KSLOT, 1);
-    kfc = kfrag(smem + KSLOT, 2);
+    kfa = kfrag<V8>(smem + kKSlot, 0, kfrag_lane);
+    kfb = kfrag<V8>(smem + kKSlot, 1, kfrag_lane);
+    kfc = kfrag<V8>(smem + kKSlot, 2, kfrag_lane);
     begin_piece();
 
     for (;;) {
@@ -710,8 +566,6 @@ __global__ __launch_bounds__(256, 1) void prefill64p_kernel(vattn_attn_params p,
     }
 #undef VATTN_GLUE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // trailing DMA retired: nothing may land in the LDS of a later workgroup
-#undef P64_X0
-#undef P64_X1
 #undef PF
 #undef PF64
 }
