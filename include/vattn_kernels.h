@@ -34,7 +34,7 @@ extern "C" {
 #define VATTN_DTYPE_F16 0
 #define VATTN_DTYPE_BF16 1
 
-#define VATTN_KERNELS_ABI 5u            /* bumped whenever vattn_attn_params changes */
+#define VATTN_KERNELS_ABI 6u            /* bumped whenever vattn_attn_params changes */
 
 typedef struct vattn_attn_params {
     /* sizeof(vattn_attn_params) and VATTN_KERNELS_ABI of the header the CALLER was built against.  The block grows between releases
@@ -117,6 +117,18 @@ typedef struct vattn_attn_params {
      * workgroups differ in speed by a few per cent).  What vattn_prefill_plan_wg(wg_first_out = NULL) prepares. */
     int32_t pf_num_wg;
     const int32_t* pf_wg_first;                    /* device: int32[pf_num_wg + 1]                                              */
+    /* Causal SLIDING WINDOW (flash_attn_interface.py:1204-1206, mask.h:36-60; both zero: no window — a zeroed block attends as before).
+     * window_left_plus1 = left + 1 > 0: query row i of a call with Sq query rows and Lk visible keys attends keys j with
+     * max(0, i + Lk - Sq - left) <= j <= i + Lk - Sq (bottom-right aligned; left = 0: the own position only).  seqlen_q > 1 needs is_causal
+     * (non-causal / right-sided windows: VATTN_K_ERR_UNSUPPORTED); the decode form ignores is_causal as it does without a window.  Not
+     * together with split_items / pf_items (VATTN_K_ERR_INVALID): a windowed key walk is bounded by left + 256 rows per query block, there
+     * is no imbalance for a host plan to remove, and the three planners return 0 ("default launch") for a block that carries a window.
+     * NO-READ CONTRACT: a windowed call issues no K or V load for a row below align_down(first key visible to the FIRST query row of
+     * batch entry b, T), T = the kernel's key tile: 32 for the decode kernels (decode_kernel, decode_stream_kernel), 64 for the prefill
+     * kernels (prefill_kernel, prefill64_kernel).  Rows inside that first tile but left of a row's limit may be loaded; they are masked
+     * before the softmax.  (What releasing the physical pages in front of the window will rest on.) */
+    int32_t window_left_plus1;
+    int32_t window_reserved;                       /* must be 0 */
 } vattn_attn_params;
 
 typedef struct vattn_prefill_item {
@@ -145,7 +157,8 @@ size_t vattn_attn_workspace_bytes(const vattn_attn_params* p);
 /* Host-side planner of the length-balanced decode split (see vattn_attn_params.split_items).  `p` describes the call (b, h, h_k, d,
  * seqlen_knew, variant; pointers are not read), cache_seqlens_host[b] are the values the device array will hold.  Writes at most
  * `cap` items and 2 * b ints of (first item, count); returns the number of items, 0 when the uniform split is at least as good
- * (equal lengths, one sequence, batches whose uniform split is already balanced) or the tables would not fit, < 0 on bad arguments.
+ * (equal lengths, one sequence, batches whose uniform split is already balanced; a block that carries a sliding window: the device
+ * plan balances by VISIBLE length, host items are refused with one) or the tables would not fit, < 0 on bad arguments.
  * p->num_splits = -T forces pieces of T tiles (tests, A/B measurements); the call itself is then made with num_splits = 0.
  * Pure host arithmetic (no device access): usable, and tested, without a GPU. */
 int32_t vattn_decode_plan(const vattn_attn_params* p, const int32_t* cache_seqlens_host, vattn_decode_item* items_out, int32_t cap,
@@ -155,7 +168,8 @@ int32_t vattn_decode_plan(const vattn_attn_params* p, const int32_t* cache_seqle
  * is_causal; pointers are not read); q_lens_host[b] are the chunk lengths (NULL: every entry has seqlen_q rows), k_lens_host[b] the
  * visible keys of each entry (cache length + new tokens).  Writes at most cap_items / cap_blocks entries and counts_out[3] =
  * {items, split blocks, partial rows}; returns the number of items, 0 when the default launch is at least as good (grids that fill
- * the chip with balanced work, short key walks, head dimensions other than 128) or a table would not fit, < 0 on bad arguments.
+ * the chip with balanced work, short key walks, head dimensions other than 128; a block that carries a sliding window: every query
+ * block's key walk is then bounded by left + 256 rows, nothing grows down the prompt) or a table would not fit, < 0 on bad arguments.
  * p->num_splits = -T forces pieces of at most T tiles (tests, A/B measurements).  Pure host arithmetic. */
 int32_t vattn_prefill_plan(const vattn_attn_params* p, const int32_t* q_lens_host, const int32_t* k_lens_host, vattn_prefill_item* items_out,
                            int32_t cap_items, vattn_prefill_item* blocks_out, int32_t cap_blocks, int32_t* counts_out);
@@ -167,7 +181,8 @@ int32_t vattn_prefill_plan(const vattn_attn_params* p, const int32_t* q_lens_hos
  * XCD's L2 keeps seeing one kv head).  items_out comes back GROUPED by workgroup; wg_first_out receives num_wg + 1 offsets — THE
  * CALLER PROVIDES ROOM FOR (max_wg > 0 ? max_wg : 256) + 1 = at most 257 int32 VALUES (the function has no capacity argument for it);
  * counts_out[4] = {items, split blocks, partial rows, num_wg}.  wg_first_out == NULL: no assignment (drawn queues, see pf_num_wg):
- * items_out stays longest first, only num_wg is chosen.  Returns the number of items (0: default launch, as above). */
+ * items_out stays longest first, only num_wg is chosen.  Returns the number of items (0: default launch, as above — always for a block
+ * that carries a sliding window: the persistent kernel is not built for one). */
 int32_t vattn_prefill_plan_wg(const vattn_attn_params* p, const int32_t* q_lens_host, const int32_t* k_lens_host, vattn_prefill_item* items_out,
                               int32_t cap_items, vattn_prefill_item* blocks_out, int32_t cap_blocks, int32_t* wg_first_out, int32_t max_wg,
                               int32_t* counts_out);

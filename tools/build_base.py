@@ -17,7 +17,9 @@ tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "vattention_amd/csrc", 
 subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
 src = open(os.path.join(tmp, "vattention_amd/build.py")).read()
 files = [x.strip().strip("\"'") for x in re.search(r"LIB_SOURCES\s*=\s*\(([^)]*)\)", src).group(1).split(",") if x.strip()]
-flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wno-unused-value", "-Wno-inline-asm", "-I" + tmp + "/include"]
+# (the product's own flags, vattention_amd/build.py build_lib — UNROLL_FLAGS included: without them the base is another binary of other code)
+flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wno-unused-value", "-Wno-inline-asm", "-mllvm", "-pragma-unroll-threshold=1000000",
+         "-I" + tmp + "/include"]
 os.makedirs(tmp + "/obj")
 
 

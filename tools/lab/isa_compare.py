@@ -2,7 +2,9 @@
 """LAB (round 6): are two device-assembly files (hipcc -S --offload-device-only) of one translation unit the same code?  Per kernel base
 name the multiset of instruction streams is compared twice: verbatim, and with immediates / offsets / labels blanked (a kernel whose
 argument list lost a parameter reads its remaining arguments at other kernarg offsets: the streams then differ in those immediates only).
-usage: isa_compare.py before.s after.s"""
+usage: isa_compare.py [--subset] before.s after.s
+--subset: `after` may hold ADDITIONAL instantiations (new template builds beside the old ones): every stream of `before` must be found among
+those of `after`; the extra ones are counted, not compared."""
 import collections
 import hashlib
 import re
@@ -37,7 +39,13 @@ def blank(v):
     return o
 
 
-def main(a_path, b_path):
+def contained(xs, ys):
+    c = collections.Counter(ys)
+    c.subtract(collections.Counter(xs))
+    return all(n >= 0 for n in c.values())
+
+
+def main(a_path, b_path, subset=False):
     a, b = kernels(a_path), kernels(b_path)
     base = lambda k: re.match(r'_ZN7vattn_k\d+(\w+?)I', k).group(1) if re.match(r'_ZN7vattn_k\d+(\w+?)I', k) else k
     ga, gb = collections.defaultdict(list), collections.defaultdict(list)
@@ -50,9 +58,17 @@ def main(a_path, b_path):
         la, lb = ga.get(name, []), gb.get(name, [])
         exact = sorted(map(h, la)) == sorted(map(h, lb))
         loose = sorted(h(blank(v)) for v in la) == sorted(h(blank(v)) for v in lb)
+        if subset and len(lb) > len(la):
+            exact = contained(list(map(h, la)), list(map(h, lb)))
+            loose = contained([h(blank(v)) for v in la], [h(blank(v)) for v in lb])
+            print('%-34s %d -> %d instantiations (%d new), instructions before %s, after %s : the %d old ones %s' % (
+                name, len(la), len(lb), len(lb) - len(la), sorted(len(v) for v in la), sorted(len(v) for v in lb), len(la),
+                'IDENTICAL' if exact else 'identical up to immediates / offsets' if loose else 'DIFFERENT'))
+            continue
         print('%-34s %d -> %d instantiations, instructions %s : %s' % (name, len(la), len(lb), sorted(len(v) for v in lb),
               'IDENTICAL' if exact else 'identical up to immediates / offsets' if loose else 'DIFFERENT'))
 
 
 if __name__ == '__main__':
-    main(sys.argv[1], sys.argv[2])
+    args = [x for x in sys.argv[1:] if x != '--subset']
+    main(args[0], args[1], subset='--subset' in sys.argv[1:])

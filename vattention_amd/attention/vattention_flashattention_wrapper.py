@@ -39,6 +39,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         self.is_metadata_initialized = False
         self.is_profiling_iteration = False
         self._rotary = None
+        self._window = None
         self._num_layers = model_config.get_num_layers(parallel_config)
         self._reset()
 
@@ -48,6 +49,20 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         cache-append launches (q and the new k rows in registers, the rotated k lands in the cache) instead of by a separate
         kernel before the wrapper (models/yi.py:172-173).  None switches back to the reference's dataflow."""
         self._rotary = cos_sin_cache
+
+    def set_sliding_window(self, left: Optional[int]) -> None:
+        """MI355X extension: causal sliding-window attention for every prefill and decode call of this wrapper — each token attends its
+        own position and the `left` positions before it (flash_attn's window_size=(left, 0); a Mistral config's sliding_window - 1).
+        An explicit opt-in: None (the default) is the reference's dataflow — its wrapper serves every model, Mistral included, with full
+        attention.  With a window the calls take the default launches (no prefill work list: the key walks are short and equal) and the
+        kernels never read K/V rows below the first tile the window touches (include/vattn_kernels.h, no-read contract)."""
+        if left is not None and int(left) < 0:
+            raise ValueError("set_sliding_window: left must be >= 0 or None")
+        self._window = None if left is None else int(left)
+        self._dec_plan = None
+
+    def _window_size(self):
+        return (-1, -1) if self._window is None else (self._window, 0)
 
     def _reset(self):
         self.prefill_query_lens: List[int] = []
@@ -164,7 +179,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
                 flash_attn_varlen_with_kvcache(query[:tok].view(tok, Hq, D), k_all, v_all, self._prefill_starts, self._prefill_qlens,
                                                max(self.prefill_query_lens), self._prefill_totals, self.batch_index[:P],
                                                softmax_scale=softmax_scale, causal=True, out=output[:tok].view(tok, Hq, D),
-                                               num_splits=num_splits, _rotary_cos_sin=self._rotary,
+                                               num_splits=num_splits, _rotary_cos_sin=self._rotary, window_size=self._window_size(),
                                                _max_seqlen_k=max(c + n for c, n in zip(self.prefill_cache_lens, self.prefill_query_lens)),
                                                _pf_plan=self._prefill_plan("varlen", self.prefill_query_lens,
                                                                            [c + n for c, n in zip(self.prefill_cache_lens, self.prefill_query_lens)], num_splits))
@@ -190,7 +205,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
                                         cache_seqlens=self.current_total_len_device_lst[i],
                                         causal=True, softmax_scale=softmax_scale,
                                         out=output[tok:tok + q_len].view(1, q_len, Hq, D), _max_seqlen_k=c_len + q_len,
-                                        num_splits=num_splits, _rotary_cos_sin=self._rotary,
+                                        num_splits=num_splits, _rotary_cos_sin=self._rotary, window_size=self._window_size(),
                                         _pf_plan=self._prefill_plan(i, [q_len], [c_len + q_len], num_splits) if q_len > 1 else None)
             tok += q_len
         return tok
@@ -199,7 +214,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         """The work list of one prefill call site of this iteration (flash_attn.prefill_plan: host arithmetic + one small H2D copy),
         built by the first layer that gets here and shared by the others — it depends on the lengths only.  None when the call cannot
         take a list anyway (an explicit split count, or the call is being recorded for the fused prefill || decode launch)."""
-        if num_splits != 0 or _FA._capture_active():
+        if num_splits != 0 or _FA._capture_active() or self._window is not None:      # (a windowed call takes the default launch)
             return None
         pl = self._pf_plans.get(key)
         if pl is None and self.head_dim == 128:
@@ -250,7 +265,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
             tm.work = self._dc_bytes
             flash_attn_with_kvcache(dq, k_all[:, :self.max_cache_len], v_all[:, :self.max_cache_len], dk, dv,
                                     cache_seqlens=self.decode_cache_lens, block_table=None,
-                                    softmax_scale=softmax_scale, causal=True,
+                                    softmax_scale=softmax_scale, causal=True, window_size=self._window_size(),
                                     cache_batch_idx=self.batch_index_gen,
                                     out=output[tok:tok + nb].view(nb, 1, Hq, D), _rotary_cos_sin=self._rotary, _params_out=capture)
             # (no host-side lengths: the launch balances a ragged batch from `cache_seqlens` on the device, csrc/decode_body.h)

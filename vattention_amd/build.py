@@ -42,7 +42,8 @@ UNROLL_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1000000"]
 # prefill64_kernel counts its own `vmcnt` around LDS-DMA issued by inline asm: a register spill (scratch access, compiler-inserted
 # waits the hand-placed ones do not know about) silently breaks it, and the kernel sits at the SGPR / VGPR limits.  Its translation unit
 # is therefore compiled with the resource-usage remarks on, and the build FAILS when any instantiation of a guarded kernel spills.
-NO_SPILL_KERNELS = {"prefill64_kernels.hip": "prefill64_kernel", "prefill64p_kernels.hip": "prefill64p_kernel", "decode_kernels.hip": "decode_"}
+NO_SPILL_KERNELS = {"prefill64_kernels.hip": "prefill64",      # prefill64_kernel and its sliding-window build prefill64w_kernel
+                     "prefill64p_kernels.hip": "prefill64p_kernel", "decode_kernels.hip": "decode_"}
 # ... except: the bf16 build of decode_stream_kernel (d = 128, one head block) that takes the fused-RoPE path at run time — bf16 rotates through fp32,
 # 12 registers more than three workgroups per CU leave; calls without rotation get the build without that path (decode_kernels.hip,
 # launch_decode_stream).  A scratch segment costs ~9 us per launch (profiles/r06_decode_bf16_scratch.txt): no other kernel may grow one unnoticed.
@@ -106,7 +107,7 @@ def _compile(hipcc, flags, src, obj):
 def build_lib(force=False):
     out = os.path.join(PKG, "libvattn_amd.so")
     srcs = [os.path.join(CSRC, f) for f in LIB_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "page_manager.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "prefill64_common.h"), os.path.join(CSRC, "prefill_body.h"), os.path.join(CSRC, "decode_body.h"),
+    deps = srcs + [os.path.join(CSRC, "page_manager.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "prefill64_common.h"), os.path.join(CSRC, "prefill64_kernel.inc"), os.path.join(CSRC, "prefill_body.h"), os.path.join(CSRC, "decode_body.h"),
                    os.path.join(ROOT, "include", "vattn.h"),
                    os.path.join(ROOT, "include", "vattn_kernels.h")]
     if force or _newer(out, deps):

@@ -263,12 +263,27 @@ int validate(const vattn_attn_params* p) {
     if (p->pf_num_wg < 0 || (p->pf_wg_first && !p->pf_num_wg) || (p->pf_num_wg && (!p->pf_items || p->pf_num_wg > p->num_pf_items)))
         return fail(VATTN_K_ERR_INVALID, "pf_num_wg (persistent work list) needs pf_items and at most one workgroup per piece; pf_wg_first needs pf_num_wg");
     if (p->split_items && p->seqlen_q != 1) return fail(VATTN_K_ERR_INVALID, "split_items (length-balanced plan) applies to the decode form only");
+    // sliding window (include/vattn_kernels.h): causal, left-sided; its key walks are short and equal, so the host plans are refused with it
+    if (p->window_left_plus1 < 0 || p->window_reserved != 0) return fail(VATTN_K_ERR_INVALID, "window_left_plus1 must be left + 1 >= 0 (0: no window) and window_reserved 0");
+    if (p->window_left_plus1 > 0) {
+        if (kLab) return fail(VATTN_K_ERR_UNSUPPORTED, "the measurement build has no sliding-window kernels (use libvattn_amd.so)");
+        if (p->seqlen_q > 1 && !p->is_causal)
+            return fail(VATTN_K_ERR_UNSUPPORTED, "a sliding window needs is_causal when seqlen_q > 1 (supported: causal windows, (left >= 0, right = 0))");
+        if (p->split_items || p->pf_items)
+            return fail(VATTN_K_ERR_INVALID, "a sliding window cannot be combined with split_items / pf_items (the planners return 0 for it: take the default launch)");
+    }
     if (!kLab) {
         const int til = (p->variant >> 1) & 7;
         if ((p->variant & ~kProductVariantMask) || !(til == 0 || til == 1 || til == 4 || til == 7))
             return fail(VATTN_K_ERR_INVALID, "variant selects a measurement build that this library does not contain (tools/lab/libvattn_lab.so, -DVATTN_LAB)");
     }
     return VATTN_K_OK;
+}
+
+// the prefill planners' answer for a block that carries a sliding window: no list, the default launch (key walks bounded by left + 256 rows)
+static int32_t window_plan_none(int32_t* counts_out, int n) {
+    for (int i = 0; counts_out && i < n; i++) counts_out[i] = 0;
+    return 0;
 }
 
 }  // namespace vattn_k
@@ -305,12 +320,14 @@ int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
 
 int32_t vattn_decode_plan(const vattn_attn_params* p, const int32_t* cache_seqlens_host, vattn_decode_item* items_out, int32_t cap, int32_t* seq_out) {
     if (!abi_ok(p)) return VATTN_K_ERR_INVALID;
+    if (p->window_left_plus1 > 0) return 0;      // windowed: the device-planned launch balances by visible length
     return decode_plan(p, cache_seqlens_host, items_out, cap, seq_out);
 }
 
 int32_t vattn_prefill_plan(const vattn_attn_params* p, const int32_t* q_lens_host, const int32_t* k_lens_host, vattn_prefill_item* items_out,
                            int32_t cap_items, vattn_prefill_item* blocks_out, int32_t cap_blocks, int32_t* counts_out) {
     if (!abi_ok(p)) return VATTN_K_ERR_INVALID;
+    if (p->window_left_plus1 > 0) return window_plan_none(counts_out, 3);
     return prefill_worklist(p, q_lens_host, k_lens_host, items_out, cap_items, blocks_out, cap_blocks, counts_out);
 }
 
@@ -318,6 +335,7 @@ int32_t vattn_prefill_plan_wg(const vattn_attn_params* p, const int32_t* q_lens_
                               int32_t cap_items, vattn_prefill_item* blocks_out, int32_t cap_blocks, int32_t* wg_first_out, int32_t max_wg,
                               int32_t* counts_out) {
     if (!abi_ok(p)) return VATTN_K_ERR_INVALID;
+    if (p->window_left_plus1 > 0) return window_plan_none(counts_out, 4);
     return prefill_worklist(p, q_lens_host, k_lens_host, items_out, cap_items, blocks_out, cap_blocks, counts_out, wg_first_out, max_wg, wg_first_out ? 1 : 2);
 }
 

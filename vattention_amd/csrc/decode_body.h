@@ -25,7 +25,11 @@ constexpr int DC_BN = 32;     // keys per wave tile
 //     launches with FEWER workgroups than the chip has room for: batch 1-4 decode; two workgroups per CU).
 // ROPE: -1 = the fused-RoPE path is compiled in and taken when p.rotary_cos_sin is set; 0 = compiled out (the bf16 build of decode_stream_kernel
 // for calls without rotation: its fp32 rotation is 12 registers more than three workgroups per CU leave, see launch_decode_stream); 1 = unconditional
-template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1>
+// WIN: causal sliding window (p.window_left_plus1 > 0; include/vattn_kernels.h) — a build of its own, so that the window-less kernels carry no
+// trace of it.  The query sits at key index Lk - 1 and sees keys [w0, Lk), w0 = max(0, Lk - (left + 1)).  The sequence's tile space starts at
+// tile0 = w0 / 32 instead of 0: splits, pieces and the stream plan divide the VISIBLE tiles [tile0, last tile], tiles below tile0 are never
+// loaded (no-read contract, T = 32), and the wave that owns tile0 masks the keys below w0 in it (taken out of the steady-state loop like the last tile).
+template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,
                                             const int item = -1, const int item_tb = 0, const int item_te = 0,
@@ -65,15 +69,17 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     // each sequence divides ITS OWN length evenly over the splits (balanced for ragged batches)
     // (stream mode: an EMPTY sequence still owns one tile of the plan's tile space — fully masked, so that its rows get written)
     const int ntiles_total = (st_mode && Lk <= 0) ? 1 : (Lk + DC_BN - 1) / DC_BN;
-    const int tiles_per_split = (ntiles_total + num_splits - 1) / num_splits;
+    const int w0 = WIN ? max(0, Lk - p.window_left_plus1) : 0;          // first visible key
+    const int tile0 = WIN ? w0 / DC_BN : 0;                             // first visible tile: pieces and splits count from here
+    const int tiles_per_split = (ntiles_total - tile0 + num_splits - 1) / num_splits;
     // item >= 0: a piece [item_tb, item_te) of a length-balanced plan (vattn_decode_plan) instead of split `split` of num_splits
     // tstride > 1 (STRIPED pieces): this workgroup's tiles are tile_begin, tile_begin + tstride, ... — the pieces of a sequence interleave
     // tile by tile instead of each streaming its own contiguous range, so that the workgroups that run together sweep ONE window of the
     // sequence (tools/decode_skew_probe.py: with contiguous ranges megabytes apart, the kv head whose bytes have address bits [9:8] = 01
     // runs 20 % behind the others and the launch waits for it).  Split mode: piece `split` of num_splits; piece mode: item_tb is the piece index.
     const bool striped = tstride > 1;
-    const int tile_begin = item >= 0 ? item_tb : (striped ? split : split * tiles_per_split);
-    const int tile_end = min(ntiles_total, item >= 0 ? item_te : (striped ? ntiles_total : tile_begin + tiles_per_split));
+    const int tile_begin = tile0 + (item >= 0 ? item_tb : (striped ? split : split * tiles_per_split));
+    const int tile_end = min(ntiles_total, item >= 0 ? (WIN ? tile0 + item_te : item_te) : (striped ? ntiles_total : tile_begin + tiles_per_split));
 
     // Fused append (seqlen_knew == 1): the new K/V row sits at key index Lk-1.  Every workgroup that reads the tile
     // holding it substitutes the row from k_new/v_new in registers; the gb == 0 workgroup also stores it into the
@@ -204,7 +210,8 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     };
     // One 32-key tile of this wave: V registers -> wave-private LDS, S^T = K.Q^T on the register-resident K fragments, request the
     // wave's next tile into the freed registers, online softmax, O^T += V^T.P^T.  RAGGED: the sequence's last tile (keys at or
-    // beyond Lk are masked) — a literal at both call sites, so the steady-state loop carries no mask and no append code.
+    // beyond Lk are masked) and, in WIN builds, its first visible one (keys below w0 are masked) — a literal at every call site, so the
+    // steady-state loop carries no mask and no append code.
     auto process_tile = [&](auto ragged_tag, const int u, const int tile, const int next_tile) {
         constexpr bool RAGGED = decltype(ragged_tag)::value;
         const int k0 = tile * DC_BN;
@@ -247,7 +254,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                 for (int kb = 0; kb < 2; kb++)
 #pragma unroll
                     for (int r = 0; r < 4; r++)
-                        if (k0 + 16 * kb + 4 * g4 + r >= Lk) s[nb][kb][r] = -INFINITY;
+                        if (k0 + 16 * kb + 4 * g4 + r >= Lk || (WIN && k0 + 16 * kb + 4 * g4 + r < w0)) s[nb][kb][r] = -INFINITY;
             }
             float mloc = -INFINITY;
 #pragma unroll
@@ -310,13 +317,23 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     const int first = __builtin_amdgcn_readfirstlane(tile_begin + wave * tstride);
     const bool own_last = special_last && last_tile >= first && last_tile < tile_end && ((last_tile - first) % wstep) == 0;
     const int loop_end = own_last ? last_tile : tile_end;          // wave-uniform
-    if (first < loop_end) {
+    int lfirst = first;                                            // first tile of the steady-state loop
+    if constexpr (WIN) {
+        // the window's first tile, when w0 is not tile-aligned, is the first tile of the wave that owns it (if it is also the sequence's
+        // last tile, the block below masks both ends)
+        if ((w0 % DC_BN) != 0 && first == tile0 && first < loop_end) {
+            load_tile(0, first);
+            process_tile(std::true_type{}, 0, first, ntiles_total);
+            lfirst = first + wstep;
+        }
+    }
+    if (lfirst < loop_end) {
 #pragma unroll
-        for (int u = 0; u < PF; u++) load_tile(u, first + u * wstep < loop_end ? first + u * wstep : ntiles_total);
-        for (int tile0 = first; tile0 < loop_end; tile0 += PF * wstep) {
+        for (int u = 0; u < PF; u++) load_tile(u, lfirst + u * wstep < loop_end ? lfirst + u * wstep : ntiles_total);
+        for (int tile_u0 = lfirst; tile_u0 < loop_end; tile_u0 += PF * wstep) {
 #pragma unroll
             for (int u = 0; u < PF; u++) {
-                const int tile = tile0 + u * wstep;
+                const int tile = tile_u0 + u * wstep;
                 if (tile >= loop_end) break;                 // wave-uniform
                 const int nxt = tile + PF * wstep;
                 process_tile(std::false_type{}, u, tile, nxt < loop_end ? nxt : ntiles_total);
@@ -523,6 +540,8 @@ struct StreamPlan {
     int incl[4], slot[4], lk[4];
     int sh, total, maxt;
 };
+// WIN: a sequence owns its VISIBLE tiles only (decode_body: [tile0, last tile]) — the plan balances by visible length.
+template <bool WIN = false>
 __device__ __forceinline__ void stream_plan_load(const vattn_attn_params& p, const int X, StreamPlan& pl) {
     const int lane = threadIdx.x & 63;
     const int B = p.b;
@@ -541,6 +560,7 @@ __device__ __forceinline__ void stream_plan_load(const vattn_attn_params& p, con
             pl.lk[e] = lk;
             pl.slot[e] = p.cache_batch_idx ? p.cache_batch_idx[i] : i;
             t = (lk > 0 ? (lk + DC_BN - 1) / DC_BN : 1);            // an empty sequence owns one (masked) tile: its rows get written
+            if constexpr (WIN) t -= max(0, lk - p.window_left_plus1) / DC_BN;
             mx = max(mx, t);
             t += X;
         }
@@ -654,7 +674,7 @@ __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, 
 
 // nwg: workgroups per (kv head, group) = gridDim.x.  The partials are merged by decode_stream_combine_kernel in a second launch (merging
 // inside the launch, XCD-consecutive ranges, per-workgroup clock stamps, fair-share issue priority: tools/lab/csrc/decode_body_lab.h).
-template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1>
+template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false>
 __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_plan[3 * DC_MAXB];                // stream mode: the plan, for the pieces after the first
@@ -667,7 +687,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     const int X = stream_switch_tiles(p);
     constexpr unsigned RB = StreamRec<NB, HD>::kFloats * 4u;
     StreamPlan pl;
-    stream_plan_load(p, X, pl);
+    stream_plan_load<WIN>(p, X, pl);
     const StreamGeom geo = stream_geom(pl.total, pl.maxt, p.b, nwg);
     // the current piece (all wave-uniform): sequence, its slot and visible length, tiles [tb, te), the sequence's records
     int b, slot, lk, tb, te, first_rec, cnt;
@@ -724,7 +744,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     for (;;) {
         const unsigned blk = stream_table_bytes(p.b) + (((unsigned)(w + b) * p.h_k + hk) * gblocks + gb) * RB;
         if (tb == 0 && hk == 0 && gb == 0 && tid == 0) stream_publish_seq(p, b, first_rec, cnt);      // (the owner of the sequence's first piece)
-        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk);
+        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk);
         if (geo.uniform || !next_piece(b + 1)) return;
         __syncthreads();                                 // the previous piece's in-workgroup merge is done with the LDS
     }
@@ -743,14 +763,14 @@ __global__ __launch_bounds__(256) void decode_stream_combine_kernel(vattn_attn_p
 
 // gblocks = head-block GROUPS per kv head (ceil(ceil(G/16) / NB)).  The partials of a split launch are merged by combine_kernel in a
 // second launch (the single-launch merges live in the lab copy).
-template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1>
+template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false>
 __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int split, hk, gb, b;
     if (p.split_items != nullptr) {
         // length-balanced plan: blockIdx.x = work item (a piece of ONE sequence), blockIdx.y = (kv head, head-block group)
         const vattn_decode_item it = p.split_items[blockIdx.x];
-        decode_body<T, HD, USE_TR, NB, W, PF>(p, 2, gblocks, fused_append, it.index_in_seq, blockIdx.y / gblocks, blockIdx.y % gblocks, it.b, smem,
+        decode_body<T, HD, USE_TR, NB, W, PF, -1, WIN>(p, 2, gblocks, fused_append, it.index_in_seq, blockIdx.y / gblocks, blockIdx.y % gblocks, it.b, smem,
                                           (int)blockIdx.x, it.tile_begin, it.tile_end);
         return;
     }
@@ -773,7 +793,7 @@ __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB >
         gb = blockIdx.y % gblocks;
         b = blockIdx.z;
     }
-    decode_body<T, HD, USE_TR, NB, W, PF>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
+    decode_body<T, HD, USE_TR, NB, W, PF, -1, WIN>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
                                           (decode_striped(p) && num_splits > 1) ? num_splits : 1);
 }
 

@@ -123,10 +123,18 @@ __global__ __launch_bounds__(128) void combine_items_kernel(vattn_attn_params p)
 // Split count for the decode form.  The kernel is built for 3 workgroups per CU (<= 168 VGPRs, 33 KiB LDS), i.e.
 // 768 resident workgroups on 256 CUs; like the reference's heuristic (flash_api.cpp:258-323) pick the smallest
 // split count whose last "round" of workgroups is nearly full, but against THIS chip's residency.
+// Rows of the cache view a sequence can have VISIBLE keys in, as far as the host knows: all of them, or — with a sliding window — the
+// left + 1 keys of the window plus the slack of its first tile (the window starts anywhere inside a 32-key tile).  What the split
+// heuristics, the stream grid and the workspace are sized by.
+static inline int decode_visible_rows(const vattn_attn_params* p) {
+    const long w = (long)p->window_left_plus1 + DC_BN - 1;
+    return (p->window_left_plus1 > 0 && w < p->seqlen_k) ? (int)w : p->seqlen_k;
+}
+
 int pick_splits(const vattn_attn_params* p, int gblocks, long slots = 768) {
     if (p->num_splits > 0) return p->num_splits > 128 ? 128 : p->num_splits;
     const long wg = (long)p->b * p->h_k * gblocks;
-    const int max_len = p->seqlen_k + p->seqlen_knew;
+    const int max_len = decode_visible_rows(p) + p->seqlen_knew;
     const int tiles = (max_len + DC_BN - 1) / DC_BN;
     long cap = tiles / 4;                       // at least one 32-key tile per wave and split
     if (cap < 1) cap = 1;
@@ -181,7 +189,7 @@ int stream_nwg(const vattn_attn_params* p) {
     // ONE sequence has nothing to balance, and the two-block workgroups of wide GQA groups (16 < G <= 32) measure 16 % slower on this path
     // (mqa G32 B16 @ 16 k: 42.5 vs 36.5 us): both keep the grid heuristics
     if (p->b < 2 || decode_nb(p) == 2) return 0;
-    const long max_tiles = std::max(1L, ((long)p->seqlen_k + DC_BN - 1) / DC_BN);      // (seqlen_k rows already hold the appended token)
+    const long max_tiles = std::max(1L, ((long)decode_visible_rows(p) + DC_BN - 1) / DC_BN);      // (seqlen_k rows already hold the appended token)
     // pieces per sequence, on average: at least one tile per wave and piece, at most 48 (pick_splits' measurements: a piece shorter than
     // ~700 keys costs more in prologue and merge than it returns once the chip is full, short contexts still want every CU busy)
     const long per_seq = std::min(48L, std::max(1L, max_tiles / 4));
@@ -193,7 +201,8 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
     return stream_table_bytes(p->b) + (size_t)(nwg + p->b) * p->h_k * rf * sizeof(float);      // (first record, count) per sequence, then the records
 }
 
-template <typename T, int HD, int NB> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg) {
+// WIN: the sliding-window builds (decode_body.h) — taken iff the block carries a window, so a window-less call runs the kernels it always ran
+template <typename T, int HD, int NB, bool WIN> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg) {
     if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
     if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
     const size_t smem = (size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2;
@@ -205,18 +214,18 @@ template <typename T, int HD, int NB> int launch_decode_stream(const vattn_attn_
         // 12 registers over the 168 of three workgroups per CU and gets a scratch segment — 9 us per launch even when no rotation is asked for
         // (profiles/r06_decode_bf16_scratch.txt).  Two builds: without the path (what the reference's wrapper calls: no spill), and the one that
         // takes it at run time (the path compiled in UNCONDITIONALLY spills more: 46 registers instead of 12).
-        if (p->rotary_cos_sin) hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, -1>), grid, block, smem, st, *p, 1, fused_append);
-        else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0>), grid, block, smem, st, *p, 1, fused_append);
-    } else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB>), grid, block, smem, st, *p, 1, fused_append);
+        if (p->rotary_cos_sin) hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, -1, WIN>), grid, block, smem, st, *p, 1, fused_append);
+        else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, WIN>), grid, block, smem, st, *p, 1, fused_append);
+    } else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, -1, WIN>), grid, block, smem, st, *p, 1, fused_append);
     hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
     return VATTN_K_OK;
 }
 
-template <typename T, int HD, int NB> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st) {
+template <typename T, int HD, int NB, bool WIN> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st) {
     constexpr int W = DC_WAVES;
-    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB>(p, st, nwg);
+    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN>(p, st, nwg);
     const int groups = decode_groups(p);
     const bool planned = p->split_items != nullptr;
     if (planned && (!p->split_seq || p->num_split_items <= 0)) return fail(VATTN_K_ERR_INVALID, "split_items needs split_seq and num_split_items");
@@ -232,7 +241,7 @@ template <typename T, int HD, int NB> int launch_decode_nb(const vattn_attn_para
     const int fused_append = (p->k_new && p->seqlen_knew == 1) ? 1 : 0;
     if (p->k_new && !fused_append) launch_append(p, st);        // seqlen_knew > 1: separate append launch
     const vattn_attn_params& q = *p;
-    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB>), grid, block, smem, st, q, splits, groups, fused_append);
+    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN>), grid, block, smem, st, q, splits, groups, fused_append);
     if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, q);
     else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, q, splits, 1);
     hipError_t e = hipGetLastError();
@@ -241,7 +250,8 @@ template <typename T, int HD, int NB> int launch_decode_nb(const vattn_attn_para
 }
 
 template <typename T, int HD> int launch_decode_t(const vattn_attn_params* p, hipStream_t st) {
-    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2>(p, st) : launch_decode_nb<T, HD, 1>(p, st);
+    if (p->window_left_plus1 > 0) return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, true>(p, st) : launch_decode_nb<T, HD, 1, true>(p, st);
+    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, false>(p, st) : launch_decode_nb<T, HD, 1, false>(p, st);
 }
 
 int launch_decode_form(const vattn_attn_params* p, hipStream_t st) {

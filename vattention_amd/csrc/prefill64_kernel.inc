@@ -1,0 +1,357 @@
+// prefill64_kernel.inc — the text of prefill64_kernel, included by prefill64_kernels.hip ONCE PER BUILD with
+//   P64_KERNEL_NAME  the kernel's name          P64_WIN  false / true (the sliding-window build)
+// Two kernels of one text, not one template with a flag and not a shared device function: the window-less kernel keeps its name and its
+// one template parameter (what the symbol checks of the test suite pin), and its machine code stays what it was — the same text as a
+// device function called from two kernels compiled to 20-100 more instructions and another register allocation.
+template <typename T>
+__global__ __launch_bounds__(256, 1) void P64_KERNEL_NAME(vattn_attn_params p, int order, int nqb, int nsplit) {
+    constexpr bool WIN = P64_WIN;
+    constexpr int NA = 24, RING = 4, MS = 8, BJ = 8, D0 = 9, DS = 3;
+    using X = Tr<T>;
+    using V8 = typename X::v8;
+    constexpr int HD = 128;
+    using S = PfSmem<HD>;
+    constexpr int BM = 256;
+    constexpr int KK = HD / 16;        // k-steps of the S^T MFMA chain
+    constexpr int DB = HD / 32;        // 32-wide d blocks of O^T
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // K ring [2][16 KiB], then V ring [3][16 KiB]; LDS address 0
+    // (no static __shared__ in this kernel: the LDS-DMA destinations are ABSOLUTE LDS addresses that assume smem starts at 0; the
+    // merge ticket lives in the 16 bytes behind the V ring)
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31;
+    const int g = lane >> 5;
+
+    int b, h, qb, split;
+    // host-planned work list (vattn_prefill_plan): blockIdx.x = one piece, longest pieces first; else the grid orders of wg_to_work
+    const bool listed = p.pf_items != nullptr;
+    int it_tb = 0, it_te = 0, it_row = -1;
+    if (listed) {
+        const vattn_prefill_item it = p.pf_items[blockIdx.x];
+        b = __builtin_amdgcn_readfirstlane(it.b);
+        h = __builtin_amdgcn_readfirstlane(it.h);
+        qb = __builtin_amdgcn_readfirstlane(it.qb);
+        it_tb = __builtin_amdgcn_readfirstlane(it.tile_begin);
+        it_te = __builtin_amdgcn_readfirstlane(it.tile_end);
+        it_row = __builtin_amdgcn_readfirstlane(it.nshares > 1 ? it.part_row : -1);
+        split = 0;
+    } else if (!wg_to_work(p, order, nqb, nsplit, b, h, qb, split)) return;
+    const bool partial = listed ? it_row >= 0 : nsplit > 1;       // this workgroup publishes an fp32 partial instead of output rows
+    const int hk = h / (p.h / p.h_k);                          // GQA: head h uses kv head h / (Hq/Hkv)
+    const int slot = __builtin_amdgcn_readfirstlane(p.cache_batch_idx ? p.cache_batch_idx[b] : b);
+    int Lk = __builtin_amdgcn_readfirstlane((p.cache_seqlens ? p.cache_seqlens[b] : p.seqlen_k) + p.seqlen_knew);
+    Lk = Lk > p.seqlen_k ? p.seqlen_k : Lk;                    // never beyond the cache view's rows
+    const int Sq = p.q_lens ? __builtin_amdgcn_readfirstlane(p.q_lens[b]) : p.seqlen_q;
+    const int64_t q_first = p.q_start ? (int64_t)__builtin_amdgcn_readfirstlane(p.q_start[b]) : 0;
+    const bool causal = p.is_causal != 0;
+    const int off = Lk - Sq;                                   // bottom-right alignment (mask.h:164-196)
+    const int q_wg0 = qb * BM;
+    if (q_wg0 >= Sq) return;                                   // shorter chunk than the grid was sized for (before any barrier)
+    const int qw0 = q_wg0 + wave * 64;                         // first query row of this wave
+
+    int n_end = Lk;
+    if (causal) n_end = min(Lk, q_wg0 + BM + off);             // last key any row of this block may see, +1
+    if (n_end < 0) n_end = 0;
+    const int nt_all = (n_end + PF_BN - 1) / PF_BN;
+    const int left = WIN ? p.window_left_plus1 - 1 : 0;
+    const int t_first = WIN ? min(nt_all, max(0, q_wg0 + off - left) >> 6) : 0;      // tile of the first key the block's first row sees
+    int tb = t_first, nt = nt_all;                             // this workgroup's key tiles [tb, nt)
+    if (listed) {
+        tb = min(nt_all, it_tb);
+        nt = min(nt_all, it_te);
+    } else if (nsplit > 1) {
+        const int per = (nt_all - t_first + nsplit - 1) / nsplit;
+        tb = min(nt_all, t_first + split * per);
+        nt = min(nt_all, tb + per);
+    }
+    const T* kbase = uniform_ptr((const T*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)hk * p.k_head_stride);
+    const T* vbase = uniform_ptr((const T*)p.v_cache + (int64_t)slot * p.v_batch_stride + (int64_t)hk * p.v_head_stride);
+    const unsigned k_rs_bytes = (unsigned)p.k_row_stride * 2u, v_rs_bytes = (unsigned)p.v_row_stride * 2u;
+
+    // ---- DMA addressing (tile-invariant per-lane offsets) ----
+    // K piece pc = 4*wave + j holds rows 4*pc .. 4*pc+3: lane i -> row 4*pc + (i & 3), 16-byte chunk i >> 2 of that row
+    // V piece pc = 4*wave + j = (d block wave, keys 16*j .. 16*j+15): lane i -> key 16*j + (i >> 2), global chunk 4*wave + (i & 3)
+    unsigned koff[4], voff[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int row = 4 * (4 * wave + j) + (lane & 3);
+        koff[j] = (unsigned)row * k_rs_bytes + (unsigned)((lane >> 2) << 4);
+        const int key = 16 * j + (lane >> 2);
+        voff[j] = (unsigned)key * v_rs_bytes + (unsigned)((4 * wave + (lane & 3)) << 4);
+    }
+    const unsigned k_lds_wave = (unsigned)(wave * 4 * kKPiece);                 // this wave's four K pieces inside a K slot
+    const unsigned v_lds_wave = (unsigned)(kVBase + wave * 4096);               // ... and V pieces inside a V slot
+    auto kslot = [&](int t) { return (t - tb) & 1; };                          // K(t)'s slot of the ring
+    auto k_rsrc = [&](int t) -> u32x4 {
+        int rem = Lk - t * PF_BN;
+        rem = rem < 0 ? 0 : (rem > PF_BN ? PF_BN : rem);
+        return tile_rsrc(kbase + (int64_t)t * PF_BN * p.k_row_stride, (unsigned)rem * k_rs_bytes);
+    };
+    auto v_rsrc = [&](int t) -> u32x4 {
+        int rem = Lk - t * PF_BN;
+        rem = rem < 0 ? 0 : (rem > PF_BN ? PF_BN : rem);
+        return tile_rsrc(vbase + (int64_t)t * PF_BN * p.v_row_stride, (unsigned)rem * v_rs_bytes);
+    };
+    auto dma_k_all = [&](int t) {      // K(t) -> K slot t & 1, this wave's four pieces
+        const u32x4 r = k_rsrc(t);
+        const unsigned l0 = k_lds_wave + (unsigned)(kslot(t) * kKSlot);
+        dma_piece_first(l0, r, koff[0]);
+        dma_piece(l0 + kKPiece, r, koff[1]);
+        dma_piece(l0 + 2 * kKPiece, r, koff[2]);
+        dma_piece(l0 + 3 * kKPiece, r, koff[3]);
+    };
+    auto dma_v_all = [&](int t) {
+        const u32x4 r = v_rsrc(t);
+        const unsigned l0 = v_lds_wave + (unsigned)(((t - tb) % 3) * S::kTileBytes);      // prologue only: V(tb) -> slot 0, V(tb+1) -> slot 1
+        dma_piece_first(l0, r, voff[0]);
+        dma_piece(l0 + 1024, r, voff[1]);
+        dma_piece(l0 + 2048, r, voff[2]);
+        dma_piece(l0 + 3072, r, voff[3]);
+    };
+
+    // ---- prologue ----
+    // A key row past the sequence's end must hold FINITE data in the V image (its probability is exactly 0, and 0 x NaN would poison
+    // O).  On gfx950 the DMA writes zeros for a lane beyond the descriptor's bound (vattn_selftest_layouts [6]); the kernel does not
+    // lean on that: a workgroup whose key range reaches the sequence's ragged last tile zero-fills the V ring first.  Every other
+    // workgroup only ever multiplies rows that the DMA fetched (tiles past `nt` are computed into S' and never used) and skips the
+    // 48 KiB of LDS writes and the barrier in front of its first fetch (below the noise in time: profiles/r03_p64_prologue_epilogue.txt).
+    if (nt * PF_BN > Lk) {
+        const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < (3 * S::kTileBytes) / (256 * 16); i++) *(uint4*)(smem + kVBase + (i * 256 + tid) * 16) = z;
+        __syncthreads();
+    }
+    // (asking for V(tb) and K(tb+1) only once Q sits in its registers — so that the wait for Q does not also wait for them — was measured:
+    // short pieces lose more on the later K(tb+1) than the first S' gains)
+    dma_k_all(tb);
+    dma_v_all(tb);
+    dma_k_all(tb + 1);
+
+    // Q^T fragments (B operand of S^T = K.Q^T): slot (g, j) <-> d = 16*kk + 8*g + j; pre-scaled into the log2 domain
+    const float escale = p.softmax_scale * kLog2e;                      // raw score -> log2 domain
+    V8 qf[2][KK];
+#pragma unroll
+    for (int qc = 0; qc < 2; qc++) {
+        const int my_q = qw0 + 32 * qc + l31;
+        const T* qptr = (const T*)p.q + (p.q_start ? 0 : (int64_t)b * p.q_batch_stride) + (q_first + my_q) * p.q_row_stride + (int64_t)h * p.q_head_stride;
+        V8 raw[KK];
+#pragma unroll
+        for (int kk = 0; kk < KK; kk++) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (my_q < Sq) {
+                v = *(const uint4*)(qptr + 16 * kk + 8 * g);
+            }
+            raw[kk] = as_v8<V8>(v);
+        }
+        if (p.rotary_cos_sin && my_q < Sq) {
+            // fused RoPE: query row i sits at position (visible keys - Sq) + i; an element and its partner d + 64 live in the same lane
+#pragma unroll
+            for (int kk = 0; kk < KK / 2; kk++) {
+                V8 c, s;
+                rope_load<T>(p, (int64_t)(off + my_q), 16 * kk + 8 * g, c, s);
+                rope8<T>(raw[kk], raw[kk + KK / 2], c, s);
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < KK; kk++) {
+            V8 sc8;
+#pragma unroll
+            for (int j = 0; j < 8; j++) sc8[j] = raw[kk][j];
+            qf[qc][kk] = sc8;
+            asm volatile("" : "+a"(qf[qc][kk]));       // materialise the fragment as ONE 4-register accumulator tuple, here
+        }
+    }
+
+    f32x16 o[DB][2];
+#pragma unroll
+    for (int i = 0; i < DB; i++)
+#pragma unroll
+        for (int qc = 0; qc < 2; qc++) o[i][qc] = (f32x16){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // -(running max) * softmax_scale * log2e of the lane's query: the addend of the exp2 argument (softmax.h:86-94)
+    float nmsub[2];
+    // lane-local partial row sums (the other half-lane holds the other 32 keys of every tile), TWO independent accumulators per
+    // query block, each touched once per MFMA group at most: with one wave per SIMD a dependent VALU chain stalls the wave, and a
+    // stalled wave issues no MFMA either
+    float l_acc[2][2];
+#pragma unroll
+    for (int qc = 0; qc < 2; qc++) {
+        nmsub[qc] = 0.f;
+#pragma unroll
+        for (int a4 = 0; a4 < 2; a4++) l_acc[qc][a4] = 0.f;
+    }
+
+    // LDS fragment addressing: one lane-dependent base per tensor + immediate offsets
+    const unsigned kfrag_lane = (unsigned)((l31 >> 2) * kKPiece + (l31 & 3) * 16 + g * 64);
+    const int i16 = lane & 15, dh = (lane >> 4) & 1;
+    const unsigned vfrag_lane = (unsigned)((4 * g + (i16 >> 2)) * 64 + (16 * dh + 4 * (i16 & 3)) * 2);
+    // masks tile tt's scores in place (ragged end of the sequence / causal diagonal) — wave-uniform decision by the caller
+    auto mask_tile = [&](int tt, f32x16 (&s)[2][2]) {
+        const int n0 = tt * PF_BN;
+#pragma unroll
+        for (int qc = 0; qc < 2; qc++) {
+            const int my_q = qw0 + 32 * qc + l31;
+            const int lim = causal ? min(Lk - 1, my_q + off) : Lk - 1;     // last visible key of this query
+            // WIN (causal; a row the chunk has ends at my_q + off <= Lk - 1): visible iff 0 <= key - (my_q + off - left) <= left — ONE unsigned
+            // compare per score, as without a window
+            const int lo = my_q + off - left;
+#pragma unroll
+            for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int key = n0 + 32 * kb + 8 * (r >> 2) + 4 * g + (r & 3);
+                    if (WIN ? (unsigned)(key - lo) > (unsigned)left : key > lim) s[kb][qc][r] = -INFINITY;
+                }
+        }
+    };
+    // tile tt needs masking (ragged end of the sequence / causal diagonal of this wave's rows) iff tt >= t_mask:
+    // 64 tt + 64 > Lk  <=>  tt >= Lk >> 6;   64 tt + 63 > qw0 + off  <=>  tt >= ((qw0 + off - 63) >> 6) + 1 (arithmetic shift)
+    const int t_mask = min(Lk >> 6, causal ? ((qw0 + off - 63) >> 6) + 1 : 0x7fffffff);
+    // WIN: ... or tt <= t_lmask, the tile that holds the left limit of the wave's LAST row (every row's first visible tile is among them)
+    const int t_lmask = WIN ? (qw0 + 63 + off - left) >> 6 : -1;
+    auto needs_mask = [&](int tt) -> bool { return tt >= t_mask || (WIN && tt <= t_lmask); };
+    // WIN: the tile that holds the first visible key of the lane's query of block qc
+    auto first_vis = [&](int qc) -> int { return max(0, qw0 + 32 * qc + l31 + off - left) >> 6; };
+
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // this wave's pieces of K(tb) landed; V(tb), K(tb+1) may still fly
+    __builtin_amdgcn_s_barrier();
+
+    f32x16 sc[2][2];      // S(t): raw scores of the current tile; becomes P(t) in place
+    f32x16 sd[2][2];
+    {
+        first_scores<T>(smem + kslot(tb) * kKSlot, sc, qf, kfrag_lane);
+        if (needs_mask(tb)) mask_tile(tb, sc);
+#pragma unroll
+        for (int qc = 0; qc < 2; qc++) {
+            const float mx = row_max(sc, qc);
+            nmsub[qc] = (mx == -INFINITY) ? 0.f : -mx * escale;     // softmax.h: a fully masked row keeps a zero reference
+        }
+    }
+
+    // the scale as a REAL scalar register: the compiler satisfies "s"(a float the VALU computed) with a vector register, and the fma then
+    // read three vector registers beside a running MFMA (and cost copies)
+    const unsigned escale_s = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, escale));
+
+    // ---- the DMA stream's scalars (tile_step, prefill64_common.h) ----
+    // rk / rv: descriptors of K(t+2) / V(t+1) at step entry (base, bytes left from the base on)
+    const unsigned k_tile_b = (unsigned)PF_BN * k_rs_bytes, v_tile_b = (unsigned)PF_BN * v_rs_bytes;
+    int k_rows_left = Lk - (tb + 2) * PF_BN, v_rows_left = Lk - (tb + 1) * PF_BN;      // rows of the sequence behind the descriptor's base
+    const unsigned long long kp0 = (unsigned long long)kbase + (unsigned long long)(tb + 2) * k_tile_b;
+    const unsigned long long vp0 = (unsigned long long)vbase + (unsigned long long)(tb + 1) * v_tile_b;
+    u32x4 rk = {(unsigned)kp0, (unsigned)(kp0 >> 32) & 0xffffu, bound(k_rows_left, k_rs_bytes), 0x00020000u};
+    u32x4 rv = {(unsigned)vp0, (unsigned)(vp0 >> 32) & 0xffffu, bound(v_rows_left, v_rs_bytes), 0x00020000u};
+    // byte offsets inside the V ring of V(t)'s slot and of the slot V(t+2) goes to (= the one V(t-1) left): slots go by (t - tb) % 3
+    unsigned vs_cur = 0, vs_dma = 2 * S::kTileBytes;
+    // One tile step of the wave: the 64 groups of tile_step, then the masking of S'(t+1) and the deferred rescale.
+    auto step = [&](int t, const int par, f32x16 (&cur)[2][2], f32x16 (&nxt)[2][2], V8& kf0, V8& kf1, V8& kf2) {
+        auto [mx0, mx1, g0, g1, grow] = tile_step<T, NA, RING, MS, BJ, D0, DS>(par, smem, cur, nxt, kf0, kf1, kf2, qf, o, l_acc, nmsub, rk, rv, k_rows_left,
+                                                                               v_rows_left, vs_cur, vs_dma, k_lds_wave, v_lds_wave, koff[0], voff[0], k_rs_bytes,
+                                                                               v_rs_bytes, k_tile_b, v_tile_b, kfrag_lane, vfrag_lane, escale_s, [](int) {});
+        if (needs_mask(t + 1)) {      // ragged end / causal diagonal: wave-uniform, the last tiles only
+            mask_tile(t + 1, nxt);
+            mx0 = row_max(nxt, 0);
+            mx1 = row_max(nxt, 1);
+            if constexpr (WIN) {      // a row's first visible tile sets its reference (see the kernel's header)
+                if (first_vis(0) == t + 1) nmsub[0] = (mx0 == -INFINITY) ? 0.f : -mx0 * escale;      // (t + 1 > tb: the walk's first tile set
+                if (first_vis(1) == t + 1) nmsub[1] = (mx1 == -INFINITY) ? 0.f : -mx1 * escale;      // its rows' references in the prologue)
+            }
+            g0 = __builtin_fmaf(mx0, escale, nmsub[0]);
+            g1 = __builtin_fmaf(mx1, escale, nmsub[1]);
+            grow = fmaxf(g0, g1);
+        }
+        if (__builtin_amdgcn_ballot_w64(grow > kDeferLog2) != 0) {          // rare: a row's maximum grew by > 2^6
+            asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");                        // every PV result has landed in O
+            SCHED_FENCE();
+            raise_max(o, l_acc, nmsub, 0, fmaxf(g0, 0.f));
+            raise_max(o, l_acc, nmsub, 1, fmaxf(g1, 0.f));
+            SCHED_FENCE();
+            asm volatile("s_nop 3" ::: "memory");                                    // accvgpr writes -> next MFMA read
+        }
+    };
+    // the loop's entry invariants: K(tb+1), V(tb) landed and known to; K(tb+2), V(tb+1) in flight; first fragments of K(tb+1) read
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                    // also: every wave is done with K(tb) (the prologue's S')
+    dma_k_all(tb + 2);
+    dma_v_all(tb + 1);
+    const char* ksm1 = smem + kslot(tb + 1) * kKSlot;
+    V8 kfa = kfrag<V8>(ksm1, 0, kfrag_lane), kfb = kfrag<V8>(ksm1, 1, kfrag_lane), kfc = kfrag<V8>(ksm1, 2, kfrag_lane);
+    for (int t = tb; t < nt; t += 2) {
+        step(t, 0, sc, sd, kfa, kfb, kfc);
+        if (t + 1 < nt) step(t + 1, 1, sd, sc, kfa, kfb, kfc);
+    }
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 7" ::: "memory");      // trailing DMA retired (nothing may land in LDS of
+    SCHED_FENCE();                                                                // a later workgroup); last PV results readable
+
+    // ---- epilogue: O^T[d = 32*db + 8*(r>>2) + 4*g + (r&3)][query] ----
+    // (Staging the fp32 partials of a key-range piece through LDS so that every store instruction writes whole 512-byte rows instead of
+    // 32 bytes of 32 rows was built and measured in round 3: no gain — the cost of the partials (no-store ablation: 5-19 % of the
+    // tensor-parallel launches, profiles/r03_p64_prologue_epilogue.txt) is their volume, not their coalescing.)
+#pragma unroll
+    for (int qc = 0; qc < 2; qc++) {
+        const int my_q = qw0 + 32 * qc + l31;
+        const float l_loc = l_acc[qc][0] + l_acc[qc][1];
+        const float l_tot = l_loc + swap_halves(l_loc);
+        const float inv = (l_tot == 0.f || l_tot != l_tot) ? 1.f : 1.f / l_tot;
+        const float m_log2 = -nmsub[qc];                      // running max of softmax_scale*log2e*q.k
+        // row of the partial buffer that query row q of this block goes to
+        auto part_row = [&](int q) -> int64_t {
+            return listed ? (int64_t)it_row + (q - q_wg0) : (((int64_t)split * p.b + b) * p.seqlen_q + q) * p.h + h;
+        };
+        float* lpart = (float*)p.workspace + (listed ? (int64_t)p.pf_part_rows : (int64_t)nsplit * p.b * p.seqlen_q * p.h) * HD;
+        if (my_q < Sq && partial) {
+            const int64_t row = part_row(my_q);
+            float* opart = (float*)p.workspace + row * HD;
+#pragma unroll
+            for (int db = 0; db < DB; db++)
+#pragma unroll
+                for (int tq = 0; tq < 4; tq++) {
+                    f32x4 w;
+#pragma unroll
+                    for (int e = 0; e < 4; e++) w[e] = o[db][qc][4 * tq + e] * inv;
+                    *(f32x4*)(opart + 32 * db + 8 * tq + 4 * g) = w;
+                }
+            if (g == 0) {
+                const float lv = (l_tot == 0.f || l_tot != l_tot) ? -INFINITY : (m_log2 + __log2f(l_tot));
+                lpart[row] = lv;
+            }
+        } else if (my_q < Sq) {
+            T* optr = (T*)p.out + (p.q_start ? 0 : (int64_t)b * p.o_batch_stride) + (q_first + my_q) * p.o_row_stride + (int64_t)h * p.o_head_stride;
+            if (((p.o_row_stride | p.o_head_stride | p.o_batch_stride) & 7) == 0) {
+                // 16-byte stores: half-lane pairs exchange 8-byte groups through v_permlane32_swap (see prefill_kernels.hip)
+#pragma unroll
+                for (int db = 0; db < DB; db++)
+#pragma unroll
+                    for (int pr = 0; pr < 2; pr++) {
+                        typename X::v4 we, wo;
+#pragma unroll
+                        for (int e = 0; e < 4; e++) {
+                            we[e] = X::cvt(o[db][qc][4 * (2 * pr) + e] * inv);
+                            wo[e] = X::cvt(o[db][qc][4 * (2 * pr + 1) + e] * inv);
+                        }
+                        uint2 ue, uo;
+                        __builtin_memcpy(&ue, &we, 8);
+                        __builtin_memcpy(&uo, &wo, 8);
+                        const auto r0 = __builtin_amdgcn_permlane32_swap(ue.x, uo.x, false, false);
+                        const auto r1 = __builtin_amdgcn_permlane32_swap(ue.y, uo.y, false, false);
+                        *(uint4*)(optr + 32 * db + 8 * (2 * pr + g)) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
+                    }
+            } else {
+#pragma unroll
+                for (int db = 0; db < DB; db++)
+#pragma unroll
+                    for (int tq = 0; tq < 4; tq++) {
+                        typename X::v4 w;
+#pragma unroll
+                        for (int e = 0; e < 4; e++) w[e] = X::cvt(o[db][qc][4 * tq + e] * inv);
+                        *(typename X::v4*)(optr + 32 * db + 8 * tq + 4 * g) = w;
+                    }
+            }
+            if (p.softmax_lse && g == 0) {
+                // natural-log LSE of scale*QK^T; +inf for fully masked rows (flash convention)
+                const float lse = (l_tot == 0.f) ? INFINITY : (m_log2 + __log2f(l_tot)) * 0.6931471805599453f;
+                p.softmax_lse[((int64_t)b * p.h + h) * p.seqlen_q + my_q] = lse;
+            }
+        }
+    }
+}

@@ -14,7 +14,11 @@ namespace vattn_k {
 // fragment, no LDS read) instead of 32 dependent v_add per tile: the kernel is VALU/issue-bound, the matrix pipe has slack.
 // The work of ONE workgroup — query block qb of head h of batch entry b, key-range share `split` of nsplit — as a device function:
 // prefill_kernel below maps blockIdx to it; hybrid_kernel (hybrid_kernels.hip) calls it from a persistent loop.
-template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM>
+// WIN: causal sliding window (p.window_left_plus1 = left + 1 > 0, is_causal set; include/vattn_kernels.h) — a build of its own.  Query row i sees
+// keys [i + off - left, i + off]: the workgroup's key walk starts at the 64-key tile that holds the first key its FIRST row sees (tiles below
+// it are never loaded: no-read contract, T = 64) and ends where it ends without a window; key-range shares divide that walk.  The left edge is
+// masked where the causal diagonal is: wave-uniform tile classes (wave_dead: wholly left of the wave's first row; need_mask: straddles some row's limit).
+template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM, bool WIN = false>
 __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const int b, const int h, const int qb, const int split, const int nsplit, char* smem) {
     using X = Tr<T>;
     using V8 = typename X::v8;
@@ -52,10 +56,12 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
     const int nt_all = (n_end + PF_BN - 1) / PF_BN;
     // KV-split: this workgroup owns key tiles [tb, nt) of the block's nt_all (an even share; shares past the end are empty
     // and fall through to the epilogue, which then publishes a zero partial with lse = -inf)
-    int tb = 0, nt = nt_all;
+    const int left = WIN ? p.window_left_plus1 - 1 : 0;
+    const int t_first = WIN ? min(nt_all, max(0, q_wg0 + off - left) / PF_BN) : 0;      // tile of the first key the block's first row sees
+    int tb = t_first, nt = nt_all;
     if (nsplit > 1) {
-        const int per = (nt_all + nsplit - 1) / nsplit;
-        tb = min(nt_all, split * per);
+        const int per = (nt_all - t_first + nsplit - 1) / nsplit;
+        tb = min(nt_all, t_first + split * per);
         nt = min(nt_all, tb + per);
     }
 
@@ -168,7 +174,7 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
 
         const int n0 = t * PF_BN;
         // wave-uniform tile classification
-        const bool wave_dead = causal && (n0 > qw0 + 32 * QC - 1 + off);          // every (row, key) pair masked
+        const bool wave_dead = (causal && (n0 > qw0 + 32 * QC - 1 + off)) || (WIN && (n0 + PF_BN - 1 < qw0 + off - left));      // every (row, key) pair masked
         if (!wave_dead) {
             const char* ksm = smem + buf * S::kBufBytes;
             const char* vsm = ksm + S::kTileBytes;
@@ -209,7 +215,7 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 2 * QC, 0);
             // s[kb][qc][r] = S^T[key = n0 + 32*kb + 8*(r>>2) + 4*g + (r&3)][query = qw0 + 32*qc + l31]
-            const bool need_mask = (n0 + PF_BN > Lk) || (causal && (n0 + PF_BN - 1 > qw0 + off));
+            const bool need_mask = (n0 + PF_BN > Lk) || (causal && (n0 + PF_BN - 1 > qw0 + off)) || (WIN && (n0 < qw0 + 32 * QC - 1 + off - left));
             float alpha[QC];
 #pragma unroll
             for (int qc = 0; qc < QC; qc++) {
@@ -221,7 +227,7 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
 #pragma unroll
                         for (int r = 0; r < 16; r++) {
                             const int key = n0 + 32 * kb + 8 * (r >> 2) + 4 * g + (r & 3);
-                            if (key > lim) s[kb][qc][r] = -INFINITY;
+                            if (key > lim || (WIN && key < my_q + off - left)) s[kb][qc][r] = -INFINITY;
                         }
                 }
                 float mloc = -INFINITY;
@@ -375,12 +381,12 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
     }
 }
 
-template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM>
+template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM, bool WIN = false>
 __global__ __launch_bounds__(64 * WAVES, (QC == 2 || HD > 128) ? 1 : 2) void prefill_kernel(vattn_attn_params p, int order, int nqb, int nsplit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int b, h, qb, split;
     if (!wg_to_work(p, order, nqb, nsplit, b, h, qb, split)) return;
-    prefill_body<T, HD, USE_TR, WAVES, QC, MSUM>(p, b, h, qb, split, nsplit, smem);      // (key-range shares are merged by combine_rows_kernel)
+    prefill_body<T, HD, USE_TR, WAVES, QC, MSUM, WIN>(p, b, h, qb, split, nsplit, smem);      // (key-range shares are merged by combine_rows_kernel)
 }
 
 }  // namespace vattn_k

@@ -152,7 +152,12 @@ PrefillPlan plan_prefill(const vattn_attn_params* p) {
     // a chunk on a long prefix then never got its key range split — 393 instead of 900-1050 TFLOP/s on a tensor-parallel shard.]
     const long lk_view = (long)p->seqlen_k + p->seqlen_knew;
     const long lk = p->max_seqlen_k_hint > 0 ? p->max_seqlen_k_hint : (lk_view > p->seqlen_q ? lk_view : p->seqlen_q);
-    const long keys = p->is_causal ? (lk - p->seqlen_q / 2) : lk;
+    long keys = p->is_causal ? (lk - p->seqlen_q / 2) : lk;
+    // sliding window: a query block walks at most the left keys in front of its first row plus its own rows — the VISIBLE keys are what the
+    // split and the tile-count gates below divide; every block then walks about the same, like a chunk on a long prefix
+    const long win_keys = p->window_left_plus1 > 0 ? (long)p->window_left_plus1 - 1 + std::min<long>(p->seqlen_q, 256) : 0;
+    const bool windowed = win_keys > 0 && win_keys < keys;
+    if (windowed) keys = win_keys;
     const long tiles = keys > 0 ? (keys + PF_BN - 1) / PF_BN : 1;
     auto cap_by_tiles = [&](long want) {                             // >= 8 tiles (512 keys) per split: below that the
         if (want > 8) want = 8;                                      // partials cost more than they return
@@ -162,7 +167,7 @@ PrefillPlan plan_prefill(const vattn_attn_params* p) {
     // equal-length work items (a chunk on a long prefix): the split count whose last round of resident workgroups is
     // fullest, smallest such count if one is (nearly) exact; unequal lengths (causal whole prompt): two rounds, so that the
     // dispatcher's heaviest-first order can even them out
-    const bool uniform = !p->is_causal || lk >= 4L * p->seqlen_q;
+    const bool uniform = !p->is_causal || lk >= 4L * p->seqlen_q || windowed;
     auto pick = [&](long wg, long slots) {
         const int cap = cap_by_tiles(8);
         if (!uniform) return cap_by_tiles((2 * slots + wg - 1) / wg);
@@ -240,7 +245,7 @@ PrefillPlan plan_prefill(const vattn_attn_params* p) {
 }
 
 // (the single-launch merge of the key-range shares — variant bits 14 / 15 — measured slower and lives in the lab copy: profiles/r02_kbench_prefill_merge.txt)
-template <typename T, int HD, int WAVES, int QC> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit) {
+template <typename T, int HD, int WAVES, int QC, bool WIN = false> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit) {
     constexpr bool MSUM = false;
     constexpr int BM = 32 * QC * WAVES;
     const int nqb = (p->seqlen_q + BM - 1) / BM;
@@ -257,11 +262,11 @@ template <typename T, int HD, int WAVES, int QC> void launch_prefill(const vattn
     }
     const size_t smem = PfSmem<HD>::kTotal;
     static const bool attr_once = [] {   // 64 KiB of dynamic LDS per workgroup
-        (void)hipFuncSetAttribute((const void*)prefill_kernel<T, HD, true, WAVES, QC, MSUM>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
+        (void)hipFuncSetAttribute((const void*)prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
         return true;
     }();
     (void)attr_once;
-    hipLaunchKernelGGL((prefill_kernel<T, HD, true, WAVES, QC, MSUM>), grid, block, smem, st, *p, order, nqb, nsplit);
+    hipLaunchKernelGGL((prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>), grid, block, smem, st, *p, order, nqb, nsplit);
     if (nsplit > 1) {
         const int64_t rows = (int64_t)p->b * p->seqlen_q * p->h;
         hipLaunchKernelGGL((combine_rows_kernel<T, HD>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, *p, nsplit, p->seqlen_q, rows);
@@ -306,8 +311,11 @@ template <typename T, int HD> int launch_prefill_t(const vattn_attn_params* p, h
             launched = true;
         }
     }
+    // (a block that carries a sliding window takes the WIN builds, a window-less one the kernels it always ran)
+    const bool win = p->window_left_plus1 > 0;
     if (launched) {
-    } else if (pl.tiling == 4) launch_prefill<T, HD, 4, 1>(p, st, pl.nsplit);
+    } else if (pl.tiling == 4) { if (win) launch_prefill<T, HD, 4, 1, true>(p, st, pl.nsplit); else launch_prefill<T, HD, 4, 1>(p, st, pl.nsplit); }
+    else if (win) launch_prefill<T, HD, 8, 1, true>(p, st, pl.nsplit);
     else launch_prefill<T, HD, 8, 1>(p, st, pl.nsplit);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));

@@ -5,7 +5,15 @@
 Signature and semantics follow /root/reference/pod_attn/pod_attn/flash_attn_interface.py:1146-1291;
 the work is done by the gfx950 kernels in libvattn_amd.so through the C ABI
 (include/vattn_kernels.h) on torch's current HIP stream.  Arguments this path never uses (paged
-block_table, alibi, sliding window, softcap, leftpad) raise NotImplementedError.
+block_table, alibi, softcap, leftpad) raise NotImplementedError.
+
+Sliding window: `window_size=(left, right)` selects causal local attention, bottom-right aligned as the
+reference states it — query row i of Sq rows over Lk visible keys attends keys
+max(0, i + Lk - Sq - left) <= j <= i + Lk - Sq.  Argument rules as flash_api.cpp:1364-1381: `causal=True`
+forces right = 0, a one-token query ignores `right`, `left >=` the cache view's row count means no window.
+Supported: left >= 0 with right = 0 after those rules (and left < 0, right < 0: no window); a window that
+reaches to the RIGHT of the diagonal (non-causal) raises NotImplementedError.  The kernels never read a key
+or value row below the first tile the window touches (include/vattn_kernels.h, "no-read contract").
 
 Rotary embedding (`rotary_cos` / `rotary_sin` [seqlen_ro, rotary_dim/2], or `_rotary_cos_sin` = the
 reference model's own cos_sin_cache [max_position, rotary_dim]) is FUSED into the launch:
@@ -74,6 +82,23 @@ def _set_cache(p, k_cache, v_cache):
     p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
     p.k_batch_stride, p.k_row_stride, p.k_head_stride = k_cache.stride(0), k_cache.stride(1), k_cache.stride(2)
     p.v_batch_stride, p.v_row_stride, p.v_head_stride = v_cache.stride(0), v_cache.stride(1), v_cache.stride(2)
+
+
+def _window_left_plus1(window_size, causal: bool, Sq: int, Sk: int):
+    """(left + 1 or 0 = no window, causal flag) of `window_size` under the reference's argument rules (flash_api.cpp:1364-1381)."""
+    left, right = (int(x) for x in window_size)
+    if causal or Sq == 1:          # :1367-1368; a one-token query has no key to the right of its own position
+        right = 0 if left >= 0 else -1
+    if left >= Sk:                 # :1380
+        left = -1
+    if right >= Sk:                # :1381
+        right = -1
+    if left < 0 and (right < 0 or causal or Sq == 1):
+        return 0, causal
+    if left < 0 or right != 0:
+        raise NotImplementedError("sliding window: only causal windows are supported — window_size=(left >= 0, 0), or any right with "
+                                  "causal=True or a one-token query; got window_size=(%d, %d) with causal=%s" % (left, right, causal))
+    return left + 1, True          # (left, 0) IS the causal mask with a left limit, whatever `causal` said (mask.h:36-60)
 
 
 _capture = None      # a list while hybrid_attn() records the two parameter blocks of a fused prefill || decode launch
@@ -176,8 +201,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     rot = _rotary_table(rotary_cos, rotary_sin, _rotary_cos_sin, rotary_interleaved, q)
     if block_table is not None:
         raise NotImplementedError("paged KV (block_table) is what vAttention replaces; not supported")
-    if alibi_slopes is not None or cache_leftpad is not None or tuple(window_size) != (-1, -1) or softcap != 0.0:
-        raise NotImplementedError("alibi / leftpad / sliding window / softcap are not used by the vAttention path")
+    if alibi_slopes is not None or cache_leftpad is not None or softcap != 0.0:
+        raise NotImplementedError("alibi / leftpad / softcap are not used by the vAttention path")
     _check_cuda(q, k_cache, v_cache, k, v)
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
@@ -241,6 +266,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
     p.softmax_lse = lse.data_ptr() if lse is not None else None
     p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, Sq, Sk, Sn, Hq, Hkv, D
+    p.window_left_plus1, causal = _window_left_plus1(window_size, bool(causal), Sq, Sk)
     p.is_causal = 1 if causal else 0
     p.dtype = K.dtype_code(q.dtype)
     p.num_splits = int(num_splits)
@@ -261,7 +287,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if rot is not None:
         p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
     plan = None
-    if Sq > 1 and D == 128 and num_splits == 0 and k is None and not _capture_active():
+    # (a sliding window takes the default launch: its key walks are short and equal, the planners answer 0 for it and the library refuses
+    # a list or host items beside one — include/vattn_kernels.h)
+    windowed = p.window_left_plus1 > 0
+    if Sq > 1 and D == 128 and num_splits == 0 and k is None and not _capture_active() and not windowed:
         # prefill form: a work list for underfilled / unbalanced grids.  `_pf_plan`: a plan object built earlier for the same lengths
         # (this package's wrapper: one per iteration), else built here — and kept, keyed on the shapes and lengths: the L layers of an
         # iteration issue the same call — from the host-side lengths when there are any (_cache_seqlens_host, or the page manager's).
@@ -275,7 +304,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
             counters["work_list_attached"] += plan.t is not None
     if Sq > 1:
         counters["prefill_calls"] += 1
-    if _cache_seqlens_host is not None and Sq == 1 and B > 1 and num_splits == 0 and not torch.cuda.is_current_stream_capturing():
+    if _cache_seqlens_host is not None and Sq == 1 and B > 1 and num_splits == 0 and not windowed and not torch.cuda.is_current_stream_capturing():
         # (the plan's tables travel by a host-to-device copy: not while the stream is being captured into a graph — the uniform split then)
         if _plan_tiles:                                        # (tests / A-B: pieces of exactly this many 32-key tiles)
             p.num_splits = -int(_plan_tiles)
@@ -477,12 +506,13 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wi
 def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q_lens: torch.Tensor, max_q_len: int,
                                    cache_seqlens: torch.Tensor, cache_batch_idx: Optional[torch.Tensor] = None,
                                    softmax_scale=None, causal=True, out=None, num_splits=0, _variant=0, _max_seqlen_k: int = 0,
-                                   _rotary_cos_sin=None, _pf_plan=None):
+                                   _rotary_cos_sin=None, _pf_plan=None, window_size=(-1, -1)):
     """MI355X extension (SURVEY §8f "batched multi-prefill"): ONE launch for the prefill chunks of several sequences with
     different lengths.  q / out are the flattened tokens [T, Hq, D]; entry i attends with rows [q_start[i], q_start[i] +
     q_lens[i]) over cache slot cache_batch_idx[i] (identity if None), keys [0, cache_seqlens[i]) — the chunk's own K/V must
     already be in the cache (cache_flat).  Bottom-right-aligned causal mask per entry, exactly as flash_attn_with_kvcache
-    does for one sequence (the reference's wrapper issues one call per prompt, vattention_flashattention_wrapper.py:129-174)."""
+    does for one sequence (the reference's wrapper issues one call per prompt, vattention_flashattention_wrapper.py:129-174).
+    `window_size=(left, right)`: causal sliding window per entry, rules as flash_attn_with_kvcache."""
     _check_cuda(q, k_cache, v_cache, q_start, q_lens, cache_seqlens, cache_batch_idx)
     if q.dim() != 3:
         raise RuntimeError("q must be [total_tokens, num_heads, head_size]")
@@ -520,6 +550,7 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q
     p.cache_batch_idx = cache_batch_idx.contiguous().data_ptr() if cache_batch_idx is not None else None
     p.q_start, p.q_lens = q_start.contiguous().data_ptr(), q_lens.contiguous().data_ptr()
     p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, int(max_q_len), Sk, 0, Hq, Hkv, D
+    p.window_left_plus1, causal = _window_left_plus1(window_size, bool(causal), int(max_q_len), Sk)
     p.is_causal = 1 if causal else 0
     p.dtype = K.dtype_code(q.dtype)
     p.num_splits = int(num_splits)
@@ -529,7 +560,7 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q
     if _rotary_cos_sin is not None:      # q rows of entry i are rotated at positions (cache_seqlens[i] - q_lens[i]) + row
         rot = _rotary_table(None, None, _rotary_cos_sin, False, q)
         p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
-    if isinstance(_pf_plan, _PrefillPlan) and D == 128 and num_splits == 0 and not _capture_active():
+    if isinstance(_pf_plan, _PrefillPlan) and D == 128 and num_splits == 0 and not _capture_active() and not p.window_left_plus1:
         _pf_plan.attach(p)        # work list built from the host-side lengths of this iteration (prefill_plan)
     _launch(p, dev, keep=(q, k_cache, v_cache, q_start, q_lens, cache_seqlens, cache_batch_idx, out, _rotary_cos_sin, _pf_plan))
     return out

@@ -10,7 +10,7 @@ from . import _lib as L
 vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
 
 
-ABI_VERSION = 5      # VATTN_KERNELS_ABI of include/vattn_kernels.h
+ABI_VERSION = 6      # VATTN_KERNELS_ABI of include/vattn_kernels.h
 
 
 class AttnParams(C.Structure):
@@ -33,6 +33,7 @@ class AttnParams(C.Structure):
         ("rotary_cos_sin", vp), ("rotary_row_stride", i64), ("rotary_dim", i32), ("rotary_reserved", i32),
         ("split_items", vp), ("split_seq", vp), ("num_split_items", i32), ("split_reserved", i32),
         ("pf_items", vp), ("pf_blocks", vp), ("num_pf_items", i32), ("num_pf_blocks", i32), ("pf_part_rows", i32), ("pf_num_wg", i32), ("pf_wg_first", vp),
+        ("window_left_plus1", i32), ("window_reserved", i32),
     ]
 
 
