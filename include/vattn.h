@@ -122,6 +122,8 @@ typedef struct vattn_stats {
     uint64_t sync_fence_ns;                   /* waiting for slot fences / device quiesce before an unmap */
     uint64_t sync_tlb_ns;                     /* TLB invalidation after unmaps */
     uint64_t sync_maps, sync_unmaps;          /* driver calls executed on the critical path */
+    uint64_t prefix_releases;                 /* vattn_release_prefix calls that released something */
+    uint64_t prefix_pages_released;           /* page positions they released */
 } vattn_stats;
 
 typedef struct vattn_handle vattn_t;
@@ -149,6 +151,36 @@ int vattn_free_batch_idx(vattn_t* m, int slot);
 /* free_batch_idx + a fence on `stream` (a hipStream_t; the stream the iteration that last reads the slot was launched on):
  * a later reclaim of the slot's pages waits for that point only instead of synchronising the whole device. */
 int vattn_free_batch_idx_on_stream(vattn_t* m, int slot, void* stream);
+/* Sliding window (MI355X extension; the reference only grows and shrinks a slot at its tail).  A slot's mapped page positions are
+ * [first, end): first is 0 until this call is made, end is what vattn_state_dump reports as `mapped`.
+ *
+ * Unmap the page positions of ACTIVE slot `slot` that lie wholly below token `keep_from_token`, return their physical pages to the
+ * pool, and report how many page positions went (0 is a normal answer).  The caller promises that no kernel launched AFTER this call
+ * reads a K/V row below keep_from_token in this slot (include/vattn_kernels.h, no-read contract: pass align_down(first visible key,
+ * 64)); kernels launched BEFORE it may still read those rows, so the unmaps wait for a fence recorded on `stream` now, exactly as the
+ * unmaps of a freed slot do.  `stream` is a hipStream_t; (void*)-1 names the legacy default stream; NULL records no fence and the
+ * unmaps wait for a device-wide quiesce instead.  Planned synchronously (bookkeeping, pool and vattn_num_free_kvblocks are up to date
+ * when the call returns), executed by the mapper thread, without joining it — unless the call reaches a position whose map is itself
+ * still queued there (later layers of a layer-ordered step, look-ahead), which the engine's rule below the window never does.
+ *   - Positions [first, P) go, P = floor(keep_from_token * row_bytes / page_size) in BYTES (row_bytes = one token's bytes in one
+ *     tensor, layers included with megacache): no byte of a row at or above keep_from_token loses its mapping, also where a row
+ *     straddles two pages.  P <= first: returns 0, no driver call, no fence recorded.
+ *   - VATTN_ERR_INVALID, nothing changed: slot out of range, inactive or reserved by vattn_premap, keep_from_token > the slot's length.
+ *   - A released position held by a vattn_map_common_pages group leaves the group; the physical pair returns to the pool with its
+ *     last mapping.
+ *   - A hole never outlives its occupant: when the slot becomes inactive (vattn_free_batch_idx[_on_stream], or a step that passes
+ *     length 0 for it) ALL its remaining pages are unmapped on the mapper thread — behind the fence the free records, or behind a
+ *     device-wide quiesce when a step dropped the slot without a free — and first returns to 0.  Inactive slots therefore always
+ *     start at position 0; the price is that such a slot hands no mapped pages to its successor (it held O(window) of them).
+ *   - vattn_step / vattn_step_async with a non-zero length below the first token that lies wholly in mapped positions
+ *     (ceil(first * page_size / row_bytes)): VATTN_ERR_INVALID before any state changes.  Tail reclamation never goes below first. */
+int64_t vattn_release_prefix(vattn_t* m, int slot, uint64_t keep_from_token, void* stream);
+/* The same for `n` slots at once, in ONE mapper batch: one wait per slot fence and one TLB step for all of them (what an engine
+ * calls once per iteration).  Every (slot, keep_from_token) pair is checked first — one invalid pair: VATTN_ERR_INVALID, nothing
+ * changed; returns the page positions released over all slots. */
+int64_t vattn_release_prefixes(vattn_t* m, const int32_t* slots, const uint64_t* keep_from_tokens, uint32_t n, void* stream);
+/* out[2*r] = first mapped page position of slot r, out[2*r+1] = one past the last; returns words written or -(words needed). */
+int64_t vattn_slot_ranges(vattn_t* m, uint64_t* out, uint64_t cap);
 /* Admission look-ahead (MI355X extension): reserve the slot alloc_new_batch_idx(seqlen) would return and map the pages `seqlen`
  * tokens need on the MAPPER thread, while the current iteration runs.  Returns the slot (-1: none free).  The slot stays
  * inactive until its length is passed to vattn_step / vattn_step_async (which then maps nothing for it on the critical
@@ -193,7 +225,7 @@ int64_t vattn_state_dump(vattn_t* m, uint64_t* out, uint64_t cap);
 int64_t vattn_pagemap_dump(vattn_t* m, uint64_t* out, uint64_t cap_rows);
 int vattn_get_stats(vattn_t* m, vattn_stats* out);
 /* O(max_batch_size) summary: out = [pool pages, sum of mapped page-groups, sum of page-groups needed by the
- * current lengths, active slots]. */
+ * current lengths, active slots].  Mapped page-groups count end - first per slot (vattn_slot_ranges). */
 int vattn_get_counts(vattn_t* m, uint64_t out[4]);
 const char* vattn_last_error(const vattn_t* m);
 /* Remap / TLB self-check of the HIP VMM backend on `device` (what vattn_create runs once per device): maps page A at a

@@ -29,11 +29,14 @@ class VattnStats(C.Structure):
                                            "unmap_calls", "sync_batches", "async_batches", "sync_ns", "async_ns",
                                            "join_wait_ns", "create_ns", "pages_mapped_now", "tlb_flushes", "tlb_flush_ns", "quiesce_calls", "quiesce_ns",
                                            "fence_waits", "fence_wait_ns", "layered_batches", "layer_wait_ns", "rollbacks",
-                                           "sync_create_ns", "sync_creates", "sync_fence_ns", "sync_tlb_ns", "sync_maps", "sync_unmaps")]
+                                           "sync_create_ns", "sync_creates", "sync_fence_ns", "sync_tlb_ns", "sync_maps", "sync_unmaps",
+                                           "prefix_releases", "prefix_pages_released")]
 
 
 VATTN_OK, VATTN_ERR_INVALID, VATTN_ERR_OOM, VATTN_ERR_DRIVER, VATTN_ERR_POOL_EMPTY = 0, -1, -2, -3, -4
 FLAG_EAGER_CREATE, FLAG_NO_ACCESS_MERGE, FLAG_NO_MAPPER_THREAD, FLAG_LAYERED_ASYNC, FLAG_NO_VMM_SELFCHECK = 1, 2, 4, 8, 16
+
+SINCE_PREFIX_RELEASE = ("vattn_release_prefix", "vattn_release_prefixes", "vattn_slot_ranges")
 
 _lib = None
 
@@ -61,6 +64,9 @@ def lib() -> C.CDLL:
         "vattn_alloc_new_batch_idx": (i32, [vp, u64]),
         "vattn_free_batch_idx": (i32, [vp, i32]),
         "vattn_free_batch_idx_on_stream": (i32, [vp, i32, vp]),
+        "vattn_release_prefix": (i64, [vp, i32, u64, vp]),
+        "vattn_release_prefixes": (i64, [vp, C.POINTER(i32), C.POINTER(u64), u32, vp]),
+        "vattn_slot_ranges": (i64, [vp, C.POINTER(u64), u64]),
         "vattn_premap": (i32, [vp, u64]),
         "vattn_wait_pool_ready": (i64, [vp, i64]),
         "vattn_cancel_premap": (i32, [vp, i32]),
@@ -85,7 +91,13 @@ def lib() -> C.CDLL:
         "vattn_hip_versions": (i32, [C.POINTER(i32), C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None:
+            # a library built before the sliding-window release (an A/B against an older build, tools/prefix_release_ab.py) has no
+            # such entry points: everything else works, a call of one of them fails with AttributeError
+            if name in SINCE_PREFIX_RELEASE:
+                continue
+            raise AttributeError("%s: symbol %s is missing" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
     _lib = L

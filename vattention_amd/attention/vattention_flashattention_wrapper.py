@@ -61,6 +61,11 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         self._window = None if left is None else int(left)
         self._dec_plan = None
 
+    @property
+    def sliding_window(self) -> Optional[int]:
+        """`left` of set_sliding_window, None = full attention (the cache engine checks it before it releases pages)."""
+        return self._window
+
     def _window_size(self):
         return (-1, -1) if self._window is None else (self._window, 0)
 

@@ -17,6 +17,7 @@ import torch
 
 from . import vattention
 from .attention import AttentionBackend, get_attention_wrapper
+from .window_release import keep_from_decode, keep_from_prompt, pages_below
 
 
 def get_cache_engine(attn_backend: str):
@@ -54,7 +55,12 @@ class vATTNCacheEngine:
         self.block_size = getattr(cache_config, "block_size", None)
         self.num_gpu_blocks = getattr(cache_config, "num_gpu_blocks", None)
         self.curr_batch_idx = None
+        self.window_left = None             # set_sliding_window
+        self.release_window_prefix = False
         self.gpu_cache = self.allocate_gpu_cache()
+        self._row_bytes = self.num_heads * self.head_size * torch.empty((), dtype=self.dtype).element_size() * (
+            self.num_layers if self.vattn_mega_cache else 1)
+        self._released = [0] * self.max_batch_size      # page positions released in front of each slot's current occupant
 
     def _apply_layout_policy(self, cache_config) -> str:
         """vattention_amd/policy.py: pools that would need > 100 k physical handles move to megacache + 8 MiB pages.  The layout is
@@ -99,25 +105,66 @@ class vATTNCacheEngine:
     def get_v_cache(self, layer_idx: int) -> torch.Tensor:
         return self.gpu_cache[layer_idx][1]
 
+    def set_sliding_window(self, left, release: bool = True) -> None:
+        """MI355X extension: serve every sequence with a causal sliding window of `left` keys before each token (one window for all
+        layers; None switches it off) and, with `release`, hand the physical pages in front of the window back to the pool as the
+        sequences grow (vattention.release_prefix).  Sets the attention wrapper's window too: pages released for `left` make any
+        attention call with a wider window, or none, read unmapped memory — if the wrapper's window is changed behind the engine's
+        back, the next step() raises instead of releasing.  Switch it on before the first request; a window cannot be widened over
+        sequences whose prefix is already gone."""
+        if left is not None and int(left) < 0:
+            raise ValueError("set_sliding_window: left must be >= 0 or None")
+        if any(self._released) and (left is None or self.window_left is None or int(left) > self.window_left):
+            raise ValueError("set_sliding_window: running sequences have already released their prefix for left = %d" % self.window_left)
+        self.window_left = None if left is None else int(left)
+        self.release_window_prefix = bool(release) and left is not None
+        get_attention_wrapper().set_sliding_window(self.window_left)
+
+    def _release_in_front_of_window(self, keep: List[Tuple[int, int]]) -> None:
+        """After this iteration's step / step_async and before its kernels are launched: the fence each release records is behind the
+        PREVIOUS iteration's kernels, the mapper thread waits for it under this iteration's forward pass, and the next step's join
+        finds the unmaps done.  All the slots of the iteration go in one call: one mapper batch, one TLB step.  The common iteration costs one integer comparison per slot."""
+        w = get_attention_wrapper().sliding_window
+        if w is None or w > self.window_left:
+            raise ValueError("the attention wrapper's sliding window (%s) is wider than the cache engine's (%d): pages in front of the "
+                             "engine's window are released, a wider attention window would read unmapped memory" % (w, self.window_left))
+        due = []
+        for slot, keep_from in keep:
+            pages = pages_below(keep_from, self._row_bytes, self.page_size)
+            if pages > self._released[slot]:
+                due.append((slot, keep_from))
+                self._released[slot] = pages      # (below what the step just mapped for the slot's length: the manager releases exactly these)
+        if due:
+            vattention.release_prefixes(due)      # one mapper batch, one TLB step, for the whole iteration
+
     def step(self, seq_metadata_list) -> None:
         idx_prompt: List[int] = []
         idx_gen: List[int] = []
+        keep: List[Tuple[int, int]] = []      # (slot, first token this iteration's kernels may read), sliding window only
+        release = self.release_window_prefix
         for md in seq_metadata_list:
             seq = md.seq
             if md.is_prompt:
-                ctx = seq.get_num_prompt_tokens_processed() + seq.get_next_prompt_chunk_len(md.prompt_chunk_len)
+                processed = seq.get_num_prompt_tokens_processed()
+                ctx = processed + seq.get_next_prompt_chunk_len(md.prompt_chunk_len)
                 slot = self.get_req_batch_idx(seq.seq_id, ctx)
                 self.curr_seq_lens[slot] = ctx
                 idx_prompt.append(slot)
+                if release:
+                    keep.append((slot, keep_from_prompt(processed, self.window_left)))
             else:
                 ctx = seq.get_len()
                 slot = self.get_req_batch_idx(seq.seq_id, ctx)
                 self.curr_seq_lens[slot] = ctx
                 idx_gen.append(slot)
+                if release:
+                    keep.append((slot, keep_from_decode(ctx, self.window_left)))
         if self.vattn_async:
             vattention.step_async(self.curr_seq_lens)
         else:
             vattention.step(self.curr_seq_lens, True)
+        if release:
+            self._release_in_front_of_window(keep)
         both = idx_prompt + idx_gen
         allidx = torch.tensor(both + idx_gen, dtype=torch.int32, device=self.device)    # ONE H2D copy
         self.curr_batch_idx = allidx[:len(both)]
@@ -156,6 +203,7 @@ class vATTNCacheEngine:
             raise Exception(f"seq_id {seq_id} not found in req_table")
         vattention.free_batch_idx(slot)
         self.curr_seq_lens[slot] = 0
+        self._released[slot] = 0              # a hole never outlives its occupant: the manager unmapped the rest (include/vattn.h)
 
     def reclaim_req_ids(self) -> None:
         for seq_id in list(self.seq_to_batch_idx):

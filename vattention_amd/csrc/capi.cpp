@@ -70,6 +70,11 @@ int vattn_wait(vattn_t* m) { return m->pm->wait(); }
 int vattn_alloc_new_batch_idx(vattn_t* m, uint64_t seqlen) { return m->pm->alloc_new_batch_idx(seqlen); }
 int vattn_free_batch_idx(vattn_t* m, int slot) { return m->pm->free_batch_idx(slot); }
 int vattn_free_batch_idx_on_stream(vattn_t* m, int slot, void* stream) { return m->pm->free_batch_idx(slot, stream, true); }
+int64_t vattn_release_prefix(vattn_t* m, int slot, uint64_t keep_from_token, void* stream) { return m->pm->release_prefix(slot, keep_from_token, stream); }
+int64_t vattn_release_prefixes(vattn_t* m, const int32_t* slots, const uint64_t* keep_from_tokens, uint32_t n, void* stream) {
+    return m->pm->release_prefixes(slots, keep_from_tokens, n, stream);
+}
+int64_t vattn_slot_ranges(vattn_t* m, uint64_t* out, uint64_t cap) { return m->pm->slot_ranges(out, cap); }
 int vattn_premap(vattn_t* m, uint64_t seqlen) { return m->pm->premap(seqlen); }
 int vattn_cancel_premap(vattn_t* m, int slot) { return m->pm->cancel_premap(slot); }
 int64_t vattn_wait_pool_ready(vattn_t* m, int64_t timeout_ms) { return m->pm->wait_pool_ready(timeout_ms); }

@@ -74,6 +74,8 @@ int PageManager::init() {
     lens_.assign(cfg_.max_batch_size, 0);
     reserved_.assign(cfg_.max_batch_size, 0);
     inherited_.assign(cfg_.max_batch_size, 0);
+    head_.assign(cfg_.max_batch_size, 0);
+    queued_from_.assign(cfg_.max_batch_size, ~0ull);
 
     const int nt = cfg_.megacache ? 2 : 2 * (int)cfg_.num_layers;
     const uint64_t align = std::max<uint64_t>(cfg_.page_size, rec_gran);
@@ -196,7 +198,54 @@ void PageManager::unmap_req_page_one(int r) {    // vattention.cu:219-241, utils
 }
 
 void PageManager::release_some(int r, uint64_t retain) {   // vattention.cu:243-247
+    if (retain < head_[r]) retain = head_[r];                // never below the first mapped position (release_prefix)
     while (mapped_pages_[r] > retain) unmap_req_page_one(r);
+}
+
+// ---- sliding window: the hole in front of an active slot (release_prefix) ----
+
+// step / step_async: a non-zero length that ends inside a slot's released prefix is refused before anything changes
+int PageManager::check_no_shrink_into_hole(const uint64_t* lens) {
+    for (int r = 0; r < (int)cfg_.max_batch_size; r++)
+        if (head_[r] != 0 && lens[r] != 0 && lens[r] < first_token_of_head(r)) {
+            std::ostringstream ss;
+            ss << "slot " << r << ": length " << lens[r] << " lies in the released prefix (first mapped token " << first_token_of_head(r) << ")";
+            return fail(VATTN_ERR_INVALID, ss.str());
+        }
+    return VATTN_OK;
+}
+
+// A hole never outlives its occupant: the slot (lens_[r] == 0 by now, so every unmap carries need_fence) gives back all it holds
+// and is an ordinary empty slot again.  state_mu_ held; the caller queues the plan for the mapper thread.
+void PageManager::close_hole(int r) {
+    while (mapped_pages_[r] > head_[r]) unmap_req_page_one(r);
+    mapped_pages_[r] = head_[r] = inherited_[r] = 0;
+}
+
+// step / step_async deactivate a slot by passing length 0 without a free_batch_idx: kernels launched since the slot's last
+// release_prefix may still read its pages and nobody recorded a later fence, so the fence is dropped (the unmaps then wait
+// for a device-wide quiesce) and the unmaps are kept apart in `later`, for the mapper thread.  `join_rc` != NULL: the caller has not
+// joined the mapper yet — a look-ahead map of such a slot's tail may still be queued and must have reached the driver (or have been
+// rolled back) before its unmap is planned, so the join happens here, once, if any slot is dropped; returns whether it did.
+bool PageManager::close_holes_of_dropped_slots(const uint64_t* lens, std::vector<PhysOp>* later, int* join_rc) {
+    bool any = false;
+    for (int r = 0; r < (int)cfg_.max_batch_size; r++) {
+        if (head_[r] == 0 || lens[r] != 0) continue;
+        if (!any && join_rc) *join_rc = wait_locked_free();
+        lens_[r] = 0;
+        if (be_.fence_record) (void)be_.fence_record(be_.ctx, (uint32_t)r, nullptr);
+        close_hole(r);
+        any = true;
+    }
+    if (any) later->swap(plan_);          // plan_ was empty: every API call leaves it flushed
+    return any;
+}
+
+void PageManager::flush_later(std::vector<PhysOp>* later) {   // state_mu_ held
+    if (later->empty()) return;
+    plan_.insert(plan_.begin(), later->begin(), later->end());
+    later->clear();
+    flush_async();
 }
 
 int PageManager::grow(int r, uint64_t nblocks, bool sync) {   // vattention.cu:268-323
@@ -235,7 +284,7 @@ void PageManager::reclaim_on_demand(uint64_t nblocks, bool allow_reserved) {   /
             if (pass == 0 && reserved_[r]) continue;
             if (pass == 1 && !reserved_[r]) continue;
             const uint64_t mapped = mapped_pages_[r];
-            const uint64_t required = tokens_to_pages(lens_[r]);
+            const uint64_t required = std::max(tokens_to_pages(lens_[r]), head_[r]);
             if (mapped <= required) continue;
             if (pass == 0) { release_some(r, required); continue; }
             while (mapped_pages_[r] > required && !kvblocks_available(nblocks)) unmap_req_page_one(r);   // only what is missing
@@ -358,8 +407,11 @@ int PageManager::step(const uint64_t* lens, uint32_t n, bool eager_reclaim) {   
     if (!inited_ || cleaned_) return fail(VATTN_ERR_INVALID, "allocator is not initialised");
     if (n != cfg_.max_batch_size) return fail(VATTN_ERR_INVALID, "seq_lens must have max_batch_size entries");
     if (fatal_.load()) return fail(fatal_.load(), last_error_);
+    if (check_no_shrink_into_hole(lens)) return VATTN_ERR_INVALID;
     int rc = wait_locked_free();
     if (rc) return rc;
+    std::vector<PhysOp> hole_unmaps;
+    close_holes_of_dropped_slots(lens, &hole_unmaps, nullptr);    // (joined above)
     int err = VATTN_OK;
     for (int r = 0; r < (int)cfg_.max_batch_size; r++) {
         lens_[r] = lens[r];
@@ -372,6 +424,7 @@ int PageManager::step(const uint64_t* lens, uint32_t n, bool eager_reclaim) {   
         if (err) break;
     }
     rc = flush_sync();
+    flush_later(&hole_unmaps);
     return err ? err : rc;
 }
 
@@ -380,11 +433,20 @@ int PageManager::step_async(const uint64_t* lens, uint32_t n) {   // vattention.
     if (!inited_ || cleaned_) return fail(VATTN_ERR_INVALID, "allocator is not initialised");
     if (n != cfg_.max_batch_size) return fail(VATTN_ERR_INVALID, "seq_lens must have max_batch_size entries");
     if (fatal_.load()) return fail(fatal_.load(), last_error_);
+    if (check_no_shrink_into_hole(lens)) return VATTN_ERR_INVALID;
+    // (a slot with a released prefix that this step drops is closed BEFORE the lengths are taken over: if the join below reports a
+    // background error and the call returns early, no slot is left inactive with a hole; the unmaps are joined by the next call)
+    std::vector<PhysOp> hole_unmaps;
+    int rc = VATTN_OK;
+    const bool joined = close_holes_of_dropped_slots(lens, &hole_unmaps, &rc);
     lens_.assign(lens, lens + n);                       // utils.h:155-158
     for (uint32_t r = 0; r < n; r++)
         if (lens[r] != 0) reserved_[r] = 0;             // a pre-mapped slot has been claimed
-    int rc = wait_locked_free();                        // wait_kvcache_manager_sync
-    if (rc) return rc;
+    if (!joined) rc = wait_locked_free();               // wait_kvcache_manager_sync
+    if (rc) {
+        flush_later(&hole_unmaps);
+        return rc;
+    }
     int err = VATTN_OK;
     for (int r = 0; r < (int)cfg_.max_batch_size; r++) {   // prepare_prefill_kvcache, :411-418
         err = map_pages_for_curr_step(r, lens_[r]);
@@ -420,12 +482,14 @@ int PageManager::step_async(const uint64_t* lens, uint32_t n) {   // vattention.
                 all.insert(all.end(), later.begin(), later.end());
                 rollback_maps(all, failed_at);
             }
+            flush_later(&hole_unmaps);
             return rc;
         }
         layered_now_ = std::move(now);                   // mapper idle (joined above) and state_mu_ held: nobody reads it now
         layered_error_.store(0);
         layers_ready_.store(sync_layers_, std::memory_order_release);
         layered_pending_.store(1, std::memory_order_release);
+        note_queued_maps(later);
         {
             std::lock_guard<std::mutex> q(q_mu_);
             queue_.push_back(std::move(later));
@@ -435,9 +499,12 @@ int PageManager::step_async(const uint64_t* lens, uint32_t n) {   // vattention.
         q_cv_.notify_all();
     } else {
         rc = flush_sync();
-        if (err) return err;
-        if (rc) return rc;
+        if (err || rc) {
+            flush_later(&hole_unmaps);
+            return err ? err : rc;
+        }
     }
+    plan_.swap(hole_unmaps);                            // (empty unless a slot with a released prefix was dropped)
     background_management();                            // planned now, executed by the mapper
     flush_async();
     return VATTN_OK;
@@ -544,14 +611,103 @@ int64_t PageManager::wait_pool_ready(int64_t timeout_ms) {
 int PageManager::free_batch_idx(int slot, void* stream, bool with_fence) {   // vattention.cu:591-594
     std::lock_guard<std::mutex> l(state_mu_);
     if (slot < 0 || slot >= (int)cfg_.max_batch_size) return fail(VATTN_ERR_INVALID, "slot out of range");
+    // a slot with a released prefix gives everything back below: a look-ahead map of its tail that is still queued must have
+    // reached the driver (or have been rolled back) before its unmap is planned
+    const int joined = head_[slot] != 0 ? wait_locked_free() : VATTN_OK;
     lens_[slot] = 0;
     reserved_[slot] = 0;
     inherited_[slot] = mapped_pages_[slot];             // whoever gets the slot next inherits these, possibly still being read
     // the point in the engine's stream after the last kernel that can read this slot's pages (plain free: no fence, a later
     // reclaim of the slot then synchronises the whole device)
-    if (be_.fence_record && be_.fence_record(be_.ctx, (uint32_t)slot, with_fence ? (stream ? stream : (void*)-1) : nullptr) != 0)
-        return fail(VATTN_ERR_DRIVER, "recording the slot fence failed");
+    // (a record that fails leaves the slot without a fence: its unmaps then wait for a device-wide quiesce)
+    const bool fence_failed = be_.fence_record && be_.fence_record(be_.ctx, (uint32_t)slot, with_fence ? (stream ? stream : (void*)-1) : nullptr) != 0;
+    if (head_[slot] != 0) {                             // a hole never outlives its occupant (release_prefix), whatever else fails
+        close_hole(slot);
+        flush_async();                                  // behind the fence just recorded, on the mapper thread
+    }
+    if (fence_failed) return fail(VATTN_ERR_DRIVER, "recording the slot fence failed");
+    return joined;
+}
+
+// include/vattn.h vattn_release_prefix / vattn_release_prefixes.  No join in the common case: the unmaps queue behind whatever the
+// mapper still holds, and its queue is one FIFO.  What must not happen is an unmap planned for a position whose MAP is still queued
+// (the later layers of a layer-ordered step, a look-ahead): if that map fails, the joiner's rollback would take the group back a
+// second time.  queued_from_[slot] is the lowest position with a map handed to the mapper since the last join; a release that
+// reaches it joins first.  The engine's rule never does: it releases below the window, the queued maps lie at the sequence's end.
+int PageManager::check_release(int slot, uint64_t keep_from_token) {
+    if (slot < 0 || slot >= (int)cfg_.max_batch_size) return fail(VATTN_ERR_INVALID, "slot out of range");
+    if (!active(slot) || reserved_[slot]) return fail(VATTN_ERR_INVALID, "release_prefix: the slot is not active");
+    if (keep_from_token > lens_[slot]) return fail(VATTN_ERR_INVALID, "release_prefix: keep_from_token exceeds the slot's length");
     return VATTN_OK;
+}
+
+int64_t PageManager::plan_release(int slot, uint64_t keep_from_token, void* stream) {   // state_mu_ held, arguments checked
+    // in BYTES: a page goes only if it ends at or below the first byte of row keep_from_token (tokens_per_page_ rounds down and
+    // would cut into that row wherever a row straddles two pages)
+    const uint64_t first = head_[slot];
+    uint64_t P = std::min(keep_from_token * row_bytes_ / cfg_.page_size, mapped_pages_[slot]);
+    if (P <= first) return 0;
+    if (P > queued_from_[slot]) {
+        int rc = wait_locked_free();
+        if (rc) return rc;
+        P = std::min(P, mapped_pages_[slot]);           // (a rollback may have taken positions back)
+        if (P <= first) return 0;
+    }
+    // kernels launched before this call may still read the rows: (void*)-1 names the legacy default stream, NULL drops the
+    // slot's fence (the unmaps then wait for a device-wide quiesce)
+    if (be_.fence_record && be_.fence_record(be_.ctx, (uint32_t)slot, stream) != 0)
+        return fail(VATTN_ERR_DRIVER, "recording the slot fence failed");
+    const uint32_t nl = cfg_.megacache ? 1 : cfg_.num_layers;
+    for (uint64_t pos = first; pos < P; pos++) {
+        const uint64_t off = (uint64_t)slot * virt_per_req_ + pos * cfg_.page_size;
+        for (uint32_t layer = 0; layer < nl; layer++) plan_unmap_pair(slot, layer, off, true);   // need_fence on every one
+        if (!shared_.empty()) forget_shared_holder(slot, pos);
+    }
+    head_[slot] = P;
+    prefix_releases_++;
+    prefix_pages_released_ += P - first;
+    return (int64_t)(P - first);
+}
+
+int64_t PageManager::release_prefix(int slot, uint64_t keep_from_token, void* stream) {
+    std::lock_guard<std::mutex> l(state_mu_);
+    if (!inited_ || cleaned_) return fail(VATTN_ERR_INVALID, "allocator is not initialised");
+    if (fatal_.load()) return fail(fatal_.load(), last_error_);
+    if (check_release(slot, keep_from_token)) return VATTN_ERR_INVALID;
+    const int64_t n = plan_release(slot, keep_from_token, stream);
+    flush_async();
+    return n;
+}
+
+// One mapper batch — one wait per slot fence, ONE TLB step — for all the slots of an iteration.
+int64_t PageManager::release_prefixes(const int32_t* slots, const uint64_t* keep_from_tokens, uint32_t n, void* stream) {
+    std::lock_guard<std::mutex> l(state_mu_);
+    if (!inited_ || cleaned_) return fail(VATTN_ERR_INVALID, "allocator is not initialised");
+    if (fatal_.load()) return fail(fatal_.load(), last_error_);
+    for (uint32_t i = 0; i < n; i++)                     // every argument first: an invalid entry changes nothing
+        if (check_release(slots[i], keep_from_tokens[i])) return VATTN_ERR_INVALID;
+    int64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const int64_t k = plan_release(slots[i], keep_from_tokens[i], stream);
+        if (k < 0) {                                     // a driver error: what is planned so far is consistent and still goes
+            flush_async();
+            return k;
+        }
+        total += k;
+    }
+    flush_async();
+    return total;
+}
+
+int64_t PageManager::slot_ranges(uint64_t* out, uint64_t cap) {
+    std::lock_guard<std::mutex> l(state_mu_);
+    const uint64_t need = 2ull * cfg_.max_batch_size;
+    if (cap < need) return -(int64_t)need;
+    for (uint64_t r = 0; r < cfg_.max_batch_size; r++) {
+        out[2 * r] = head_[r];
+        out[2 * r + 1] = mapped_pages_[r];
+    }
+    return (int64_t)need;
 }
 
 uint64_t PageManager::num_free_kvblocks() {   // vattention.cu:189-210, utils.h:177-183 (u64 wrap kept)
@@ -654,7 +810,10 @@ int PageManager::cleanup() {   // vattention.cu:601-609, mux.h:24-35, cudaIntern
     std::lock_guard<std::mutex> l(state_mu_);
     if (!inited_ || cleaned_) return VATTN_OK;
     wait_locked_free();
-    for (int r = 0; r < (int)cfg_.max_batch_size; r++) release_some(r, 0);
+    for (int r = 0; r < (int)cfg_.max_batch_size; r++) {
+        release_some(r, 0);
+        mapped_pages_[r] = head_[r] = 0;                // (release_some stops at the first mapped position)
+    }
     int rc = flush_sync();
     {
         std::lock_guard<std::mutex> e(exec_mu_);
@@ -714,7 +873,7 @@ void PageManager::counts(uint64_t out[4]) {
     out[0] = pool_.size();
     out[1] = out[2] = out[3] = 0;
     for (uint32_t r = 0; r < cfg_.max_batch_size; r++) {
-        out[1] += mapped_pages_[r];
+        out[1] += mapped_pages_[r] - head_[r];
         out[2] += tokens_to_pages(lens_[r]);
         out[3] += lens_[r] != 0;
     }
@@ -725,6 +884,8 @@ void PageManager::stats(vattn_stats* out) {
     *out = st_;
     out->join_wait_ns = join_wait_ns_.load();
     out->layer_wait_ns = layer_wait_ns_.load();
+    out->prefix_releases = prefix_releases_.load();
+    out->prefix_pages_released = prefix_pages_released_.load();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -929,8 +1090,17 @@ void PageManager::rollback_maps(const std::vector<PhysOp>& ops, size_t first_fai
     st_.rollbacks++;
 }
 
+void PageManager::note_queued_maps(const std::vector<PhysOp>& ops) {   // state_mu_ held
+    for (const PhysOp& op : ops) {
+        if (op.kind != 0) continue;
+        const uint64_t pos = (op.offset - (uint64_t)op.slot * virt_per_req_) / cfg_.page_size;
+        if (pos < queued_from_[op.slot]) queued_from_[op.slot] = pos;
+    }
+}
+
 int PageManager::wait_locked_free() {   // state_mu_ held; joins every queued background batch
     const uint64_t t0 = now_ns();
+    std::fill(queued_from_.begin(), queued_from_.end(), ~0ull);
     std::vector<PhysOp> failed;
     std::vector<std::vector<PhysOp>> later;
     size_t failed_at = 0;
@@ -996,6 +1166,7 @@ void PageManager::flush_async() {   // state_mu_ held
         }
         return;
     }
+    note_queued_maps(ops);
     {
         std::lock_guard<std::mutex> q(q_mu_);
         queue_.push_back(std::move(ops));

@@ -49,6 +49,9 @@ public:
     int wait();
     int alloc_new_batch_idx(uint64_t seqlen);
     int free_batch_idx(int slot, void* stream = nullptr, bool with_fence = false);
+    int64_t release_prefix(int slot, uint64_t keep_from_token, void* stream);   // include/vattn.h vattn_release_prefix
+    int64_t release_prefixes(const int32_t* slots, const uint64_t* keep_from_tokens, uint32_t n, void* stream);
+    int64_t slot_ranges(uint64_t* out, uint64_t cap);
     int premap(uint64_t seqlen);
     int cancel_premap(int slot);
     int64_t wait_pool_ready(int64_t timeout_ms);      // include/vattn.h vattn_wait_pool_ready
@@ -80,6 +83,12 @@ private:
 
     // ---- bookkeeping state (utils.h:12-81) ----
     std::vector<uint64_t> mapped_pages_, lens_;
+    // Sliding window (release_prefix, no reference counterpart): slot r's mapped page positions are [head_[r], mapped_pages_[r]).
+    // head_ is 0 everywhere until release_prefix is called and 0 for every INACTIVE slot (a hole never outlives its occupant:
+    // close_hole), so the routines that mirror the reference see the prefix [0, mapped_pages_[r]) they were written for.
+    std::vector<uint64_t> head_;
+    std::atomic<uint64_t> prefix_releases_{0}, prefix_pages_released_{0};
+    std::vector<uint64_t> queued_from_;       // per slot: lowest page position with a map handed to the mapper since the last join (~0: none)
     std::vector<uint32_t> pool_;                                  // LIFO of page ids
     std::map<std::tuple<uint64_t, uint64_t, uint64_t>, std::pair<uint32_t, uint32_t>> pagemap_;
     bool deferred_reclaim_ = true, verbose_ = false;
@@ -120,6 +129,16 @@ private:
     void rollback_maps(const std::vector<PhysOp>& ops, size_t first_failed);   // state_mu_ held
     void unmap_req_page_one(int r);
     void release_some(int r, uint64_t retain);
+    uint64_t first_token_of_head(int r) const {   // first token whose row lies wholly at or above slot r's first mapped position
+        return (head_[r] * cfg_.page_size + row_bytes_ - 1) / row_bytes_;
+    }
+    int check_no_shrink_into_hole(const uint64_t* lens);
+    int check_release(int slot, uint64_t keep_from_token);
+    int64_t plan_release(int slot, uint64_t keep_from_token, void* stream);
+    void note_queued_maps(const std::vector<PhysOp>& ops);
+    void close_hole(int r);                    // slot r (head_ > 0) became inactive: plan the unmap of everything it still holds
+    bool close_holes_of_dropped_slots(const uint64_t* lens, std::vector<PhysOp>* later, int* join_rc);
+    void flush_later(std::vector<PhysOp>* later);
     int grow(int r, uint64_t nblocks, bool sync);
     void reclaim_on_demand(uint64_t nblocks, bool allow_reserved = true);
     void do_reclaim_pages();

@@ -86,6 +86,35 @@ class PageManager:
         else:
             self._check(self._lib.vattn_free_batch_idx_on_stream(self._h, int(slot), C.c_void_p(stream)))
 
+    def release_prefix(self, slot: int, keep_from_token: int, stream: Optional[int] = None) -> int:
+        """Unmap the page positions of active `slot` that lie wholly below token `keep_from_token`; returns how many went (include/vattn.h,
+        vattn_release_prefix).  `stream` (a raw hipStream_t, 0 = the default stream): the unmaps wait for the kernels launched on it so
+        far; None: for the whole device."""
+        st = None if stream is None else C.c_void_p(stream if stream else -1)      # (void*)-1 names the default stream
+        n = int(self._lib.vattn_release_prefix(self._h, int(slot), int(keep_from_token), st))
+        if n < 0:
+            self._check(n)
+        return n
+
+    def release_prefixes(self, pairs: Sequence[tuple], stream: Optional[int] = None) -> int:
+        """release_prefix for several (slot, keep_from_token) pairs in ONE mapper batch (one TLB step); returns the positions released."""
+        n = len(pairs)
+        if n == 0:
+            return 0
+        slots = (C.c_int32 * n)(*[int(s) for s, _ in pairs])
+        keeps = (C.c_uint64 * n)(*[int(k) for _, k in pairs])
+        st = None if stream is None else C.c_void_p(stream if stream else -1)
+        got = int(self._lib.vattn_release_prefixes(self._h, slots, keeps, n, st))
+        if got < 0:
+            self._check(got)
+        return got
+
+    def ranges(self) -> List[tuple]:
+        """(first mapped page position, one past the last) of every slot."""
+        buf = (C.c_uint64 * (2 * self.max_batch_size))()
+        self._lib.vattn_slot_ranges(self._h, buf, 2 * self.max_batch_size)
+        return [(int(buf[2 * r]), int(buf[2 * r + 1])) for r in range(self.max_batch_size)]
+
     def premap(self, seqlen: int) -> int:
         return self._lib.vattn_premap(self._h, int(seqlen))
 

@@ -129,8 +129,12 @@ class ReplayStats:
 class HotPathRunner:
     """Owns the cache engine + wrapper for one GPU and replays scheduler iterations."""
 
-    def __init__(self, model: ModelConfig, parallel: ParallelConfig, cache: CacheConfig, device="cuda:0", seed=42, reference=None):
-        """reference: None = this package's wrapper + cache engine; else an object with `.wrapper` (an attention-wrapper INSTANCE) and
+    def __init__(self, model: ModelConfig, parallel: ParallelConfig, cache: CacheConfig, device="cuda:0", seed=42, reference=None,
+                 sliding_window: Optional[int] = None, release_prefix: bool = True):
+        """sliding_window: None = full attention; else every sequence is served with a causal window of that many keys before each token
+        (cache_engine.set_sliding_window) and, with release_prefix, the pages in front of the window go back to the pool as the
+        sequences grow — release_prefix=False runs the same windowed kernels over fully mapped sequences (the A/B control).
+        reference: None = this package's wrapper + cache engine; else an object with `.wrapper` (an attention-wrapper INSTANCE) and
         `.engine_cls` — tools/ref_wrapper_bench.py passes the REFERENCE's own classes (tests/ref_loader.py), which only know the
         reference's API: no admission look-ahead, no layer-ordered mapping, no host-side hints."""
         from .attention import get_attention_wrapper, set_attention_backend
@@ -149,6 +153,10 @@ class HotPathRunner:
             self.wrapper.init(model, parallel, 0, self.device)
             eng = get_cache_engine(model.attention_backend)
             self.engine = eng(cache, model, parallel, get_cache_mem_alloc_backend(model.attention_backend))
+            if sliding_window is not None:
+                self.engine.set_sliding_window(sliding_window, release=release_prefix)
+        if sliding_window is not None and reference is not None:
+            raise ValueError("the reference's wrapper and cache engine know no sliding window")
         self.Hq = model.get_num_q_heads(parallel)
         self.Hkv = model.get_num_kv_heads(parallel)
         self.D = model.get_head_size()

@@ -127,6 +127,26 @@ def free_batch_idx(reqId: int) -> None:
     pm.free_batch_idx(reqId, stream=torch.cuda.current_stream(pm.cfg.device).cuda_stream)
 
 
+def release_prefix(reqId: int, keep_from_token: int) -> int:
+    """MI355X extension (include/vattn.h, vattn_release_prefix): unmap the page positions of active slot `reqId` that lie wholly
+    below token `keep_from_token` and return their physical pages to the pool; returns how many page positions went.  The caller
+    promises that no kernel launched after this call reads a K/V row of the slot below keep_from_token; kernels launched so far on
+    torch's current stream may, and the unmaps (on the mapper thread) wait for them."""
+    pm = _require()
+    return pm.release_prefix(reqId, keep_from_token, stream=torch.cuda.current_stream(pm.cfg.device).cuda_stream)
+
+
+def release_prefixes(pairs) -> int:
+    """release_prefix for the (reqId, keep_from_token) pairs of one iteration in ONE mapper batch: one TLB step for all of them."""
+    pm = _require()
+    return pm.release_prefixes(pairs, stream=torch.cuda.current_stream(pm.cfg.device).cuda_stream)
+
+
+def slot_ranges():
+    """(first mapped page position, one past the last) of every slot."""
+    return _require().ranges()
+
+
 def num_free_kvblocks() -> int:
     return _require().num_free_kvblocks()
 
