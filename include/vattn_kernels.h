@@ -191,11 +191,11 @@ int32_t vattn_prefill_plan_wg(const vattn_attn_params* p, const int32_t* q_lens_
  * test can pin the launch plans without a GPU and without a stopwatch (tests/test_plan_table.py; the reference's equivalents are the
  * launch heuristics of flash_api.cpp:258-323 and flash_fwd_launch_template.h:100-162).  Returns 0, or VATTN_K_ERR_INVALID. */
 typedef struct vattn_plan_desc {
-    int32_t form;          /* 0 = prefill (seqlen_q > 1), 1 = decode                                                              */
+    int32_t form;          /* 0 = prefill (seqlen_q > 1), 1 = the decode kernels: seqlen_q == 1, or the multi-token form           */
     int32_t path;          /* prefill: 0 = grid order, 1 = work list (pf_items).  decode: 0 = uniform split of every sequence (grid
                               heuristics), 1 = host item plan (split_items), 2 = device-planned stream decomposition               */
     int32_t tiling;        /* prefill: 1 = 8 waves x 32 rows, 4 = 4 waves x 32 rows, 7 = prefill64 (4 waves x 64 rows).
-                              decode: 16-head blocks per workgroup (1 or 2)                                                        */
+                              decode: 16-head blocks per workgroup (1 or 2; multi-token form: 16-column blocks)                   */
     int32_t nsplit;        /* key-range shares per work item of the grid paths (1 = none); 0 on the list / item / stream paths      */
     int32_t workgroups;    /* workgroups of the main launch that hold work (grid padding excluded)                                 */
     int32_t merge_launch;  /* 1 = a second launch merges fp32 partials                                                             */
@@ -204,7 +204,22 @@ typedef struct vattn_plan_desc {
 int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
 
 /* flash_attn_with_kvcache: appends k_new/v_new (if given) and attends; prefill form (seqlen_q > 1,
- * causal chunk against the growing cache) and decode form (seqlen_q == 1, split-KV + combine). */
+ * causal chunk against the growing cache) and decode form (seqlen_q == 1, split-KV + combine).
+ *
+ * MULTI-TOKEN FORM (the verify step of speculative decoding / multi-token prediction: a few query rows per entry against a long
+ * cache).  The split-KV decode kernels run the call — the MFMA columns that hold a kv head's G = h / h_k query heads hold
+ * seqlen_q * G (token, head) pairs, every K/V row is read once per kv head — instead of the prefill kernels' 128- / 256-row query
+ * blocks.  GATE, all of: 2 <= seqlen_q <= 8 and seqlen_q * G <= 64; q_lens, pf_items, split_items and rotary_cos_sin NULL; `variant`
+ * tiling bits 1-3 zero; num_splits <= 0 (< 0 keeps its decode meaning: forced workgroups per kv head / pieces); the product library (a
+ * -DVATTN_LAB build has no such kernels).  Every other block behaves as before: an explicit prefill tiling or num_splits > 0 keeps the
+ * prefill kernels for the same call (the A/B selector), as do fused-rotary calls; split_items and vattn_hybrid_attn's decode block stay
+ * seqlen_q == 1.  vattn_attn_workspace_bytes and vattn_attn_plan_describe (form 1) answer for the form the call will take.
+ * VISIBILITY: with Lk = cache_seqlens[b] + seqlen_knew visible keys, query row t sees keys j <= Lk - seqlen_q + t when is_causal and
+ * all j < Lk otherwise; with window_left_plus1 > 0 (needs is_causal) also j >= max(0, Lk - seqlen_q + t - left).  A row without a
+ * visible key (Lk - seqlen_q + t < 0) gives 0 and LSE +inf.  out[b, t, h, :] through o_row_stride; softmax_lse [b, h, seqlen_q].
+ * APPEND: k_new / v_new (seqlen_knew rows, any count) land at rows cache_seqlens[b] .. before the attention launch on the same stream,
+ * bit-exact, nothing else in the cache is touched.  CONTRACT: as everywhere — no K/V load at or beyond Lk; in a windowed call none
+ * below align_down(first key visible to the entry's FIRST query row, 32). */
 int vattn_flash_attn_with_kvcache(const vattn_attn_params* p, void* stream);
 
 /* Fused prefill || decode for a hybrid batch (replaces the reference's POD-Attention entry point

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel microbenchmark (GPU): times the attention kernels through the C ABI with HIP events
 (vattn_time_attn) on the shapes of BASELINE.md §3 and prints TFLOP/s / GB/s against the rooflines.
-usage: python tools/kbench.py [prefill] [decode] [--variant N]"""
+usage: python tools/kbench.py [prefill] [decode] [--variant N]
+       python tools/kbench.py multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base LIB] [--bf16]   (the multi-token decode form)"""
 import ctypes as C
 import os
 import sys
@@ -166,6 +167,63 @@ def decode(variant):
         del keep, kc, vc
 
 
+def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
+    """The multi-token decode call (q [B, sq, Hq, 128] against `ctx` cached tokens, the sq new rows appended) on caches that ROTATE (as
+    --rotate: the Infinity Cache serves no repeat): this tree, the one-token decode step of the same batch, the prefill form of the same
+    call (variant 8: what answered it before the form existed), the call and the one-token step WITHOUT k / v (same visible lengths, no
+    append) and — with --base PATH, a library built from another commit (tools/build_base.py) — that library's default launch of the same block.  ragged: lengths spread over [ctx / 8, ctx]."""
+    torch.manual_seed(0)
+    slots = B
+    by1 = B * 2.0 * ctx * Hkv * 128 * 2
+    R = max(2, int(1.5e9 // by1) + 1)
+    caches = [(torch.randn(slots, ctx + sq, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(slots, ctx + sq, Hkv, 128, device=DEV, dtype=DTYPE)) for _ in range(R)]
+    lens = [ctx - (i * 7919 % (ctx - ctx // 8)) for i in range(B)] if ragged else [ctx] * B
+    cl = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    idx = torch.arange(B, dtype=torch.int32, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    libs = [("this tree", K.klib())] + ([("base", K._bind(C.CDLL(base_path)))] if base_path else [])
+
+    def run(label, lib, n, variant, append=True):
+        q = torch.randn(B, n, Hq, 128, device=DEV, dtype=DTYPE)
+        kn, vn = torch.randn(B, n, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, n, Hkv, 128, device=DEV, dtype=DTYPE)
+        ps = []
+        for kc, vc in caches:
+            # (without k / v the rows are taken as already in the cache: the same visible length, no append)
+            p, keep = params(q, kc, vc, cl, idx, kn, vn, variant=variant) if append else params(q, kc, vc, cl + n, idx, variant=variant)
+            p.max_seqlen_k_hint = 0
+            need = lib.vattn_attn_workspace_bytes(C.byref(p))          # (the library that runs the call sizes its workspace)
+            w = torch.empty(need // 4 + 1, dtype=torch.float32, device=DEV)
+            p.workspace = w.data_ptr()
+            ps.append((p, keep, w))
+        d = K.describe(ps[0][0], lib)
+        best = []
+        for _rep in range(3):
+            for pp, _k, _w in ps:
+                if lib.vattn_flash_attn_with_kvcache(C.byref(pp), st) != 0:
+                    raise RuntimeError(K.last_error(lib))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            iters = max(2, 40 // R + 1)
+            e0.record()
+            for _ in range(iters):
+                for pp, _k, _w in ps:
+                    lib.vattn_flash_attn_with_kvcache(C.byref(pp), st)
+            e1.record()
+            torch.cuda.synchronize()
+            best.append(e0.elapsed_time(e1) / (iters * R) * 1e3)
+        print("  %-34s form %d path %d tiling %d wg %5d : %8.1f us  (3 runs: %s)" % (label, d["form"], d["path"], d["tiling"], d["workgroups"], min(best),
+                                                                                  " ".join("%.1f" % x for x in best)), flush=True)
+    print("== multi-token decode B=%d sq=%d %d/%d heads ctx=%d%s, %s, D=128, %d rotating caches ==" % (
+        B, sq, Hq, Hkv, ctx, " ragged" if ragged else "", "bf16" if DTYPE == torch.bfloat16 else "fp16", R), flush=True)
+    for name, lib in libs:
+        run("%s: the call (default plan)" % name, lib, sq, 0)
+    run("this tree: prefill form (variant 8)", K.klib(), sq, 8)
+    run("this tree: one-token decode step", K.klib(), 1, 0)
+    # the same two launches without k / v: what the append costs in each form (a launch of its own in front of the multi-token call, fused
+    # into the one-token step), apart from what the attention launches themselves cost
+    run("this tree: the call, no k/v", K.klib(), sq, 0, append=False)
+    run("this tree: one-token step, no k/v", K.klib(), 1, 0, append=False)
+
+
 ONLY = None
 ROTATE = False
 WORKLIST = False
@@ -202,6 +260,22 @@ if __name__ == "__main__":
     VARIANTS = [variant] if "--variant" in sys.argv else [0, 8, 12]
     if "--variants" in sys.argv:
         VARIANTS = [int(x) for x in sys.argv[sys.argv.index("--variants") + 1].split(",")]
+    if "multitoken" in sys.argv:
+        # multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base build/base/libvattn_amd.so] [--bf16]
+        base = sys.argv[sys.argv.index("--base") + 1] if "--base" in sys.argv else None
+        shapes = []
+        for i, a in enumerate(sys.argv):
+            if a == "--mt":
+                f = sys.argv[i + 1].split(",") if i + 1 < len(sys.argv) else []
+                if len(f) not in (5, 6) or not all(x.isdigit() for x in f[:5]) or (len(f) == 6 and f[5] != "ragged"):
+                    sys.exit("kbench multitoken: --mt takes B,sq,Hq,Hkv,ctx[,ragged] (five integers), got %r" % ",".join(f))
+                shapes.append(([int(x) for x in f[:5]], len(f) == 6))
+        if not shapes:
+            sys.exit("kbench multitoken: give at least one --mt B,sq,Hq,Hkv,ctx[,ragged]")
+        torch.zeros(1, device=DEV)
+        for dims, ragged in shapes:
+            multitoken(*dims, ragged=ragged, base_path=base)
+        sys.exit(0)
     what = [a for a in sys.argv[1:] if a in ("prefill", "decode")] or ["prefill", "decode"]
     torch.zeros(1, device=DEV)
     if "prefill" in what:

@@ -1,6 +1,7 @@
 // C ABI of the gfx950 attention kernels over virtually-contiguous KV tensors (include/vattn_kernels.h).
 //   prefill_kernels.hip : seqlen_q > 1   (chunked causal prefill, KV split, batched variable-length chunks)
-//   decode_kernels.hip  : seqlen_q == 1  (split-KV decode with in-kernel append, combine)
+//   decode_kernels.hip  : seqlen_q == 1  (split-KV decode with in-kernel append, combine), and the multi-token form: 2..8 query rows
+//                         per entry as (token, head) columns of the same kernels (multitoken_form, attn_common.h)
 //   cache_kernels.hip   : cache_flat / append
 // Semantics follow the operator the reference calls (flash_attn_with_kvcache):
 //   /root/reference/pod_attn/pod_attn/flash_attn_interface.py:1146-1291, flash_api.cpp:1291-1578,
@@ -297,7 +298,7 @@ const char* vattn_kernels_last_error(void) { return g_err.c_str(); }
 size_t vattn_attn_workspace_bytes(const vattn_attn_params* p) {
     if (!abi_ok(p)) return 0;
     if (!p || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0) return 0;
-    return p->seqlen_q != 1 ? prefill_workspace_bytes(p) : decode_workspace_bytes(p);
+    return decode_form(p) ? decode_workspace_bytes(p) : prefill_workspace_bytes(p);
 }
 
 int vattn_flash_attn_with_kvcache(const vattn_attn_params* p, void* stream) {
@@ -305,14 +306,14 @@ int vattn_flash_attn_with_kvcache(const vattn_attn_params* p, void* stream) {
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
-    return p->seqlen_q == 1 ? launch_decode_form(p, st) : launch_prefill_form(p, st);
+    return decode_form(p) ? launch_decode_form(p, st) : launch_prefill_form(p, st);
 }
 
 int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (!p || !out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || (p->d != 64 && p->d != 128)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_plan_describe: bad shape");
     memset(out, 0, sizeof *out);
-    if (p->seqlen_q == 1) decode_describe(p, out);
+    if (decode_form(p)) decode_describe(p, out);
     else prefill_describe(p, out);
     out->workspace_bytes = (int64_t)vattn_attn_workspace_bytes(p);
     return VATTN_K_OK;

@@ -41,6 +41,18 @@ constexpr bool kLab = false;
 constexpr int kVariantLegacyDecodePlan = 1 << 19, kVariantInLaunchMerge = 1 << 20;
 constexpr int kProductVariantMask = (7 << 1) | (3 << 5) | (1 << 7) | (3 << 12) | kVariantLegacyDecodePlan;
 
+// The MULTI-TOKEN decode form (include/vattn_kernels.h): a few query rows per entry against a long cache — the verify step of speculative
+// decoding / multi-token prediction — run by the split-KV decode kernels with (token, head) columns (decode_body.h, MT) instead of the
+// prefill kernels' 128- / 256-row query blocks.  THE gate: everything that routes a block (launch, workspace size, plan description, the
+// Python drop-in through the plan description) asks this one function.  An explicit prefill tiling or num_splits > 0 keeps the prefill
+// form (which is also the A/B selector), as do fused-rotary calls, the batched-chunk form and the work lists; the lab build has no such kernels.
+inline bool multitoken_form(const vattn_attn_params* p) {
+    if (kLab || p->h_k <= 0 || p->h < p->h_k) return false;
+    return p->seqlen_q >= 2 && p->seqlen_q <= 8 && (long)p->seqlen_q * (p->h / p->h_k) <= 64 && !p->q_lens && !p->pf_items && !p->split_items &&
+           !p->rotary_cos_sin && ((p->variant >> 1) & 7) == 0 && p->num_splits <= 0;
+}
+inline bool decode_form(const vattn_attn_params* p) { return p->seqlen_q == 1 || multitoken_form(p); }
+
 template <typename T> struct Tr;
 template <> struct Tr<_Float16> {
     using v8 = f16x8;
@@ -269,7 +281,7 @@ void launch_prefill64(const vattn_attn_params* p, hipStream_t st, int nsplit);  
 void launch_prefill64(const vattn_attn_params* p, hipStream_t st, int nsplit, int* done, int merge_mode);   // tools/lab/csrc/prefill64_lab.hip; done: counters of the single-launch merge or NULL
 #endif
 int* merge_counters(hipStream_t st, size_t n_ints);                      // attn_api.hip: zeroed per-(device, stream) counters, NULL while capturing
-int launch_decode_form(const vattn_attn_params* p, hipStream_t st);     // decode_kernels.hip (seqlen_q == 1)
+int launch_decode_form(const vattn_attn_params* p, hipStream_t st);     // decode_kernels.hip (decode_form(p): seqlen_q == 1, or the multi-token form)
 size_t decode_workspace_bytes(const vattn_attn_params* p);
 int decode_plan(const vattn_attn_params* p, const int32_t* lens, vattn_decode_item* items, int cap, int32_t* seq);   // decode_kernels.hip
 void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out);   // prefill_kernels.hip

@@ -29,7 +29,16 @@ constexpr int DC_BN = 32;     // keys per wave tile
 // trace of it.  The query sits at key index Lk - 1 and sees keys [w0, Lk), w0 = max(0, Lk - (left + 1)).  The sequence's tile space starts at
 // tile0 = w0 / 32 instead of 0: splits, pieces and the stream plan divide the VISIBLE tiles [tile0, last tile], tiles below tile0 are never
 // loaded (no-read contract, T = 32), and the wave that owns tile0 masks the keys below w0 in it (taken out of the steady-state loop like the last tile).
-template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false>
+// MT: the MULTI-TOKEN form (2 <= seqlen_q <= 8 query rows per entry: the verify step of speculative decoding; include/vattn_kernels.h) — a
+// build of its own, the one-token kernels carry no trace of it.  The MFMA N dimension holds R = seqlen_q * G columns, TOKEN-MAJOR: column
+// c <-> (token t = c / G, head g = c % G) — the G heads of one token are then one contiguous run of q and of out (head stride apart, as in
+// the one-token form), and a token's columns share one pair of mask bounds.  Token t of an entry with Lk visible keys sees keys
+// j < hi_t = Lk - (seqlen_q - 1) + t when is_causal (all j < Lk otherwise) and, in WIN builds, j >= hi_t - (left + 1).  Only the tiles that
+// hold a key at or beyond hi_0 (at most two, at the tail) and, in WIN builds, below token seqlen_q - 1's first key (at most two, at the
+// front) take the masked path, where every lane compares against ITS column's bounds; waves interleave tile by tile (or further apart),
+// so a wave owns at most one tile of each pair, and it is its last resp. first tile.  The first visible key of the ENTRY is token 0's
+// (tile0, the no-read contract).  No fused append, no fused rotation: the host launches the append first (launch_append).
+template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,
                                             const int item = -1, const int item_tb = 0, const int item_te = 0,
@@ -54,6 +63,8 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     const int g4 = lane >> 4;
 
     const int G = p.h / p.h_k;
+    const int R = MT ? p.seqlen_q * G : G;               // live columns of the kv head
+    const int qoff = MT ? p.seqlen_q - 1 : 0;            // query rows behind the entry's first one
     int slot, Lk;
     if (st_mode) {
         slot = st_slot;
@@ -69,7 +80,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     // each sequence divides ITS OWN length evenly over the splits (balanced for ragged batches)
     // (stream mode: an EMPTY sequence still owns one tile of the plan's tile space — fully masked, so that its rows get written)
     const int ntiles_total = (st_mode && Lk <= 0) ? 1 : (Lk + DC_BN - 1) / DC_BN;
-    const int w0 = WIN ? max(0, Lk - p.window_left_plus1) : 0;          // first visible key
+    const int w0 = WIN ? max(0, (MT ? Lk - qoff : Lk) - p.window_left_plus1) : 0;   // first visible key (MT: of the entry's first query row)
     const int tile0 = WIN ? w0 / DC_BN : 0;                             // first visible tile: pieces and splits count from here
     const int tiles_per_split = (ntiles_total - tile0 + num_splits - 1) / num_splits;
     // item >= 0: a piece [item_tb, item_te) of a length-balanced plan (vattn_decode_plan) instead of split `split` of num_splits
@@ -93,12 +104,16 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     V8 qf[NB][KK];
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) {
-        const int row_head = (gb * NB + nb) * 16 + l15;     // query head within the group handled by this lane's column
+        const int row_head = (gb * NB + nb) * 16 + l15;     // query head within the group handled by this lane's column (MT: column)
         const T* qptr = (const T*)p.q + (int64_t)b * p.q_batch_stride + (int64_t)(hk * G + row_head) * p.q_head_stride;
+        if constexpr (MT) {
+            const int t = row_head / G;
+            qptr = (const T*)p.q + (int64_t)b * p.q_batch_stride + (int64_t)t * p.q_row_stride + (int64_t)(hk * G + row_head - t * G) * p.q_head_stride;
+        }
 #pragma unroll
         for (int kk = 0; kk < KK; kk++) {
             uint4 v = make_uint4(0, 0, 0, 0);
-            if (row_head < G) v = *(const uint4*)(qptr + 32 * kk + 8 * g4);
+            if (row_head < R) v = *(const uint4*)(qptr + 32 * kk + 8 * g4);
             qf[nb][kk] = as_v8<V8>(v);
         }
     }
@@ -249,12 +264,26 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
         V8 pf[NB];
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) {
-            if (RAGGED) {
+            if (RAGGED && !MT) {
 #pragma unroll
                 for (int kb = 0; kb < 2; kb++)
 #pragma unroll
                     for (int r = 0; r < 4; r++)
                         if (k0 + 16 * kb + 4 * g4 + r >= Lk || (WIN && k0 + 16 * kb + 4 * g4 + r < w0)) s[nb][kb][r] = -INFINITY;
+            }
+            if constexpr (MT) {
+                if (RAGGED) {
+                    // this lane's column sees keys [lo, hi) — derived here, in the at most two masked tiles of a wave, instead of living
+                    // in registers through the key walk
+                    const int t = min(((gb * NB + nb) * 16 + l15) / G, qoff);
+                    const int hi = p.is_causal ? Lk - qoff + t : Lk;
+                    const int lo = hi - p.window_left_plus1;        // (WIN only)
+#pragma unroll
+                    for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++)
+                            if (k0 + 16 * kb + 4 * g4 + r >= hi || (WIN && k0 + 16 * kb + 4 * g4 + r < lo)) s[nb][kb][r] = -INFINITY;
+                }
             }
             float mloc = -INFINITY;
 #pragma unroll
@@ -315,13 +344,27 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     const bool special_last = fused_append || (Lk % DC_BN) != 0 || Lk <= 0;
     const int wstep = __builtin_amdgcn_readfirstlane(W * tstride);          // distance between two tiles of one wave
     const int first = __builtin_amdgcn_readfirstlane(tile_begin + wave * tstride);
-    const bool own_last = special_last && last_tile >= first && last_tile < tile_end && ((last_tile - first) % wstep) == 0;
-    const int loop_end = own_last ? last_tile : tile_end;          // wave-uniform
+    bool own_last = special_last && last_tile >= first && last_tile < tile_end && ((last_tile - first) % wstep) == 0;
+    int tail_tile = last_tile;                                     // the masked tail tile this wave owns, if own_last
+    if constexpr (MT) {
+        // tail tiles: those that hold a key some column cannot see — keys from hi_0 = Lk - (seqlen_q - 1) on (causal), or the keys at or
+        // beyond Lk of a ragged last tile.  seqlen_q - 1 < 32: at most the last two tiles; a wave's tiles are >= 4 apart: it owns at most one
+        const int mask_from = p.is_causal ? max(0, Lk - qoff) : Lk;
+        const int t0 = mask_from / DC_BN, t1 = t0 + 1;
+        const bool own0 = t0 <= last_tile && t0 >= first && t0 < tile_end && ((t0 - first) % wstep) == 0;
+        const bool own1 = t1 <= last_tile && t1 >= first && t1 < tile_end && ((t1 - first) % wstep) == 0;
+        own_last = own0 || own1;
+        tail_tile = own1 ? t1 : t0;
+    }
+    const int loop_end = own_last ? tail_tile : tile_end;          // wave-uniform
     int lfirst = first;                                            // first tile of the steady-state loop
     if constexpr (WIN) {
         // the window's first tile, when w0 is not tile-aligned, is the first tile of the wave that owns it (if it is also the sequence's
-        // last tile, the block below masks both ends)
-        if ((w0 % DC_BN) != 0 && first == tile0 && first < loop_end) {
+        // last tile, the block below masks both ends).  MT: every tile that starts below the LAST token's first key (tile0 or tile0 + 1:
+        // the first tile of whichever wave owns it)
+        bool own_first = (w0 % DC_BN) != 0 && first == tile0 && first < loop_end;
+        if constexpr (MT) own_first = first * DC_BN < Lk - p.window_left_plus1 && first < loop_end;
+        if (own_first) {
             load_tile(0, first);
             process_tile(std::true_type{}, 0, first, ntiles_total);
             lfirst = first + wstep;
@@ -341,9 +384,9 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
         }
     }
     if (own_last) {
-        load_tile(0, last_tile);
-        if (fused_append) substitute_new_row(last_tile * DC_BN);
-        process_tile(std::true_type{}, 0, last_tile, ntiles_total);
+        load_tile(0, tail_tile);
+        if (!MT && fused_append) substitute_new_row(tail_tile * DC_BN);
+        process_tile(std::true_type{}, 0, tail_tile, ntiles_total);
     }
 
     // ---- merge the W waves (each holds a partial softmax over its own tiles), one head block after the other ----
@@ -373,7 +416,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
             for (int i4 = tid; i4 < 16 * (HD / 4); i4 += 64 * W) {
                 const int row = i4 / (HD / 4), d0 = (i4 % (HD / 4)) * 4;
                 const int rh = (gb * NB + nb) * 16 + row;
-                if (rh >= G) continue;
+                if (rh >= R) continue;
                 float mx = -INFINITY;
 #pragma unroll
                 for (int w = 0; w < W; w++) mx = fmaxf(mx, msm[w * 16 + row]);
@@ -388,7 +431,8 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                     for (int e = 0; e < 4; e++) acc[e] += f * a[e];
                     lsum += f * lsm[w * 16 + row];
                 }
-                const int hh = hk * G + rh;
+                const int tq = MT ? rh / G : 0;                   // column -> (token, head)
+                const int hh = hk * G + rh - tq * G;
                 const float inv = (lsum == 0.f || lsum != lsum) ? 1.f : 1.f / lsum;
 #pragma unroll
                 for (int e = 0; e < 4; e++) acc[e] *= inv;
@@ -396,9 +440,9 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                     typename X::v4 o4;
 #pragma unroll
                     for (int e = 0; e < 4; e++) o4[e] = X::cvt(acc[e]);
-                    *(typename X::v4*)((T*)p.out + (int64_t)b * p.o_batch_stride + (int64_t)hh * p.o_head_stride + d0) = o4;
+                    *(typename X::v4*)((T*)p.out + (int64_t)b * p.o_batch_stride + (MT ? (int64_t)tq * p.o_row_stride : 0) + (int64_t)hh * p.o_head_stride + d0) = o4;
                     if (p.softmax_lse && d0 == 0)
-                        p.softmax_lse[(int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * p.softmax_scale + __logf(lsum));
+                        p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * p.softmax_scale + __logf(lsum));
                 } else {
                     // record block: float o[16 * NB][HD], then float lse[16 * NB] (log2 domain) — see decode_stream_kernel
                     const unsigned r16 = (unsigned)(nb * 16 + row);
@@ -414,7 +458,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
         for (int idx = tid; idx < 16 * HD; idx += 64 * W) {
             const int row = idx / HD, d = idx % HD;
             const int rh = (gb * NB + nb) * 16 + row;
-            if (rh >= G) continue;
+            if (rh >= R) continue;
             float mx = -INFINITY;
 #pragma unroll
             for (int w = 0; w < W; w++) mx = fmaxf(mx, msm[w * 16 + row]);
@@ -426,16 +470,19 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                 acc += f * osm[(w * 16 + row) * HD + d];
                 lsum += f * lsm[w * 16 + row];
             }
-            const int hh = hk * G + rh;
+            const int tq = MT ? rh / G : 0;                       // column -> (token, head)
+            const int hh = hk * G + rh - tq * G;
             const float inv = (lsum == 0.f || lsum != lsum) ? 1.f : 1.f / lsum;
             if (num_splits == 1 && item < 0) {
-                ((T*)p.out)[(int64_t)b * p.o_batch_stride + (int64_t)hh * p.o_head_stride + d] = X::cvt(acc * inv);
+                ((T*)p.out)[(int64_t)b * p.o_batch_stride + (MT ? (int64_t)tq * p.o_row_stride : 0) + (int64_t)hh * p.o_head_stride + d] = X::cvt(acc * inv);
                 if (p.softmax_lse && d == 0)
-                    p.softmax_lse[(int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * p.softmax_scale + __logf(lsum));
+                    p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * p.softmax_scale + __logf(lsum));
             } else {
                 float* oacc = (float*)p.workspace;
-                float* lacc = oacc + (item >= 0 ? (int64_t)p.num_split_items : (int64_t)num_splits * p.b) * p.h * HD;
-                const int64_t row_idx = item >= 0 ? (int64_t)item * p.h + hh : ((int64_t)split * p.b + b) * p.h + hh;
+                // (MT: combine_kernel's layout for seqlen_q rows per entry: partial rows [split][b][token][head])
+                float* lacc = oacc + (item >= 0 ? (int64_t)p.num_split_items : (int64_t)num_splits * p.b * (MT ? p.seqlen_q : 1)) * p.h * HD;
+                const int64_t row_idx = item >= 0 ? (int64_t)item * p.h + hh
+                                                  : MT ? (((int64_t)split * p.b + b) * p.seqlen_q + tq) * p.h + hh : ((int64_t)split * p.b + b) * p.h + hh;
                 const float lv = (lsum == 0.f) ? -INFINITY : (mxs + __log2f(lsum));   // log2 domain
                 oacc[row_idx * HD + d] = acc * inv;
                 if (d == 0) lacc[row_idx] = lv;
@@ -541,7 +588,7 @@ struct StreamPlan {
     int sh, total, maxt;
 };
 // WIN: a sequence owns its VISIBLE tiles only (decode_body: [tile0, last tile]) — the plan balances by visible length.
-template <bool WIN = false>
+template <bool WIN = false, bool MT = false>
 __device__ __forceinline__ void stream_plan_load(const vattn_attn_params& p, const int X, StreamPlan& pl) {
     const int lane = threadIdx.x & 63;
     const int B = p.b;
@@ -560,7 +607,7 @@ __device__ __forceinline__ void stream_plan_load(const vattn_attn_params& p, con
             pl.lk[e] = lk;
             pl.slot[e] = p.cache_batch_idx ? p.cache_batch_idx[i] : i;
             t = (lk > 0 ? (lk + DC_BN - 1) / DC_BN : 1);            // an empty sequence owns one (masked) tile: its rows get written
-            if constexpr (WIN) t -= max(0, lk - p.window_left_plus1) / DC_BN;
+            if constexpr (WIN) t -= max(0, lk - (MT ? p.seqlen_q - 1 : 0) - p.window_left_plus1) / DC_BN;
             mx = max(mx, t);
             t += X;
         }
@@ -612,20 +659,21 @@ __device__ __forceinline__ void stream_publish_seq(const vattn_attn_params& p, c
 // 256-thread workgroup: a thread owns four columns of one head row, walks the records in chunks of CH with every load of a chunk
 // in flight at once (device-scope loads: the records were written by other workgroups of this launch) and folds the chunks together
 // like an online softmax (running maximum, running weight sum) — any number of records, one pass.
-template <typename T, int HD, int NB, int CH = 8, int SCOPE = kDevScope>
+template <typename T, int HD, int NB, int CH = 8, int SCOPE = kDevScope, bool MT = false>
 __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, const int first_rec, const int cnt, const int hk, const int gb,
                                                     const int gblocks, const int b) {
     using X = Tr<T>;
     constexpr int RF = StreamRec<NB, HD>::kFloats;
     const int tid = threadIdx.x;
     const int G = p.h / p.h_k;
+    const int R = MT ? p.seqlen_q * G : G;      // live columns (decode_body)
     const __amdgpu_buffer_rsrc_t wsr = make_rsrc(p.workspace, 0x7fffffffu);
     const unsigned blk_stride = (unsigned)p.h_k * (unsigned)gblocks * RF * 4u;                 // bytes between consecutive records
     const unsigned blk0 = stream_table_bytes(p.b) + ((unsigned)first_rec * p.h_k * gblocks + (unsigned)hk * gblocks + gb) * RF * 4u;
     for (int i4 = tid; i4 < 16 * NB * (HD / 4); i4 += 256) {
         const int r16 = i4 / (HD / 4), d0 = (i4 % (HD / 4)) * 4;
         const int rh = gb * NB * 16 + r16;
-        if (rh >= G) continue;
+        if (rh >= R) continue;
         const unsigned o_off = blk0 + (unsigned)(r16 * HD + d0) * 4u, l_off = blk0 + (unsigned)(16 * NB * HD + r16) * 4u;
         float m = -INFINITY, wsum = 0.f;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -662,19 +710,20 @@ __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, 
             m = m_new;
         }
         const float inv = (wsum == 0.f) ? 0.f : 1.f / wsum;
-        const int hh = hk * G + rh;
+        const int tq = MT ? rh / G : 0;          // column -> (token, head)
+        const int hh = hk * G + rh - tq * G;
         typename X::v4 o4;
 #pragma unroll
         for (int e = 0; e < 4; e++) o4[e] = X::cvt(acc[e] * inv);
-        *(typename X::v4*)((T*)p.out + (int64_t)b * p.o_batch_stride + (int64_t)hh * p.o_head_stride + d0) = o4;
+        *(typename X::v4*)((T*)p.out + (int64_t)b * p.o_batch_stride + (MT ? (int64_t)tq * p.o_row_stride : 0) + (int64_t)hh * p.o_head_stride + d0) = o4;
         if (p.softmax_lse && d0 == 0)
-            p.softmax_lse[(int64_t)b * p.h + hh] = (wsum == 0.f) ? INFINITY : (((m == -INFINITY) ? 0.f : m) + __log2f(wsum)) * 0.6931471805599453f;
+            p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (wsum == 0.f) ? INFINITY : (((m == -INFINITY) ? 0.f : m) + __log2f(wsum)) * 0.6931471805599453f;
     }
 }
 
 // nwg: workgroups per (kv head, group) = gridDim.x.  The partials are merged by decode_stream_combine_kernel in a second launch (merging
 // inside the launch, XCD-consecutive ranges, per-workgroup clock stamps, fair-share issue priority: tools/lab/csrc/decode_body_lab.h).
-template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false>
+template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false>
 __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_plan[3 * DC_MAXB];                // stream mode: the plan, for the pieces after the first
@@ -687,7 +736,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     const int X = stream_switch_tiles(p);
     constexpr unsigned RB = StreamRec<NB, HD>::kFloats * 4u;
     StreamPlan pl;
-    stream_plan_load<WIN>(p, X, pl);
+    stream_plan_load<WIN, MT>(p, X, pl);
     const StreamGeom geo = stream_geom(pl.total, pl.maxt, p.b, nwg);
     // the current piece (all wave-uniform): sequence, its slot and visible length, tiles [tb, te), the sequence's records
     int b, slot, lk, tb, te, first_rec, cnt;
@@ -744,7 +793,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     for (;;) {
         const unsigned blk = stream_table_bytes(p.b) + (((unsigned)(w + b) * p.h_k + hk) * gblocks + gb) * RB;
         if (tb == 0 && hk == 0 && gb == 0 && tid == 0) stream_publish_seq(p, b, first_rec, cnt);      // (the owner of the sequence's first piece)
-        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk);
+        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk);
         if (geo.uniform || !next_piece(b + 1)) return;
         __syncthreads();                                 // the previous piece's in-workgroup merge is done with the LDS
     }
@@ -752,22 +801,22 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
 
 // The merge as a second launch: one workgroup per (sequence, kv head x group) merges the sequence's records (nothing to do for sequences
 // that one workgroup wrote directly).
-template <typename T, int HD, int NB>
+template <typename T, int HD, int NB, bool MT = false>
 __global__ __launch_bounds__(256) void decode_stream_combine_kernel(vattn_attn_params p, int gblocks) {
     const int b = blockIdx.x, hk = blockIdx.y / gblocks, gb = blockIdx.y % gblocks;
     const int* t = (const int*)p.workspace + 2 * b;
     const int first_rec = __builtin_amdgcn_readfirstlane(t[0]), cnt = __builtin_amdgcn_readfirstlane(t[1]);
     if (cnt <= 1) return;
-    decode_stream_merge<T, HD, NB, 16, 0>(p, first_rec, cnt, hk, gb, gblocks, b);      // (up to 16 records in ONE round trip)
+    decode_stream_merge<T, HD, NB, 16, 0, MT>(p, first_rec, cnt, hk, gb, gblocks, b);      // (up to 16 records in ONE round trip)
 }
 
 // gblocks = head-block GROUPS per kv head (ceil(ceil(G/16) / NB)).  The partials of a split launch are merged by combine_kernel in a
 // second launch (the single-launch merges live in the lab copy).
-template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false>
+template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false>
 __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int split, hk, gb, b;
-    if (p.split_items != nullptr) {
+    if (!MT && p.split_items != nullptr) {          // (host items: the one-token form only)
         // length-balanced plan: blockIdx.x = work item (a piece of ONE sequence), blockIdx.y = (kv head, head-block group)
         const vattn_decode_item it = p.split_items[blockIdx.x];
         decode_body<T, HD, USE_TR, NB, W, PF, -1, WIN>(p, 2, gblocks, fused_append, it.index_in_seq, blockIdx.y / gblocks, blockIdx.y % gblocks, it.b, smem,
@@ -793,7 +842,7 @@ __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB >
         gb = blockIdx.y % gblocks;
         b = blockIdx.z;
     }
-    decode_body<T, HD, USE_TR, NB, W, PF, -1, WIN>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
+    decode_body<T, HD, USE_TR, NB, W, PF, MT ? 0 : -1, WIN, MT>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
                                           (decode_striped(p) && num_splits > 1) ? num_splits : 1);
 }
 

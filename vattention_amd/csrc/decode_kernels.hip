@@ -1,4 +1,5 @@
-// Decode form (seqlen_q == 1) of flash_attn_with_kvcache on gfx950: GQA group packed into the MFMA N dimension, split-KV over
+// Decode form (seqlen_q == 1, and the multi-token form: 2 <= seqlen_q <= 8 rows per entry as (token, head) columns, multitoken_form in
+// attn_common.h) of flash_attn_with_kvcache on gfx950: GQA group packed into the MFMA N dimension, split-KV over
 // the context, K fragments loaded straight from HBM into MFMA operand registers, V through a wave-private LDS transpose
 // stage, fp32 online softmax, in-workgroup merge of the 4 waves, new K/V row appended in-kernel, LSE-weighted combine across
 // splits (combine_kernel; flash_fwd_kernel.h:1116-1297).  Call-site semantics: flash_api.cpp:1367-1378,1451-1454,1558-1560.
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(128) void combine_items_kernel(vattn_attn_params p)
 // left + 1 keys of the window plus the slack of its first tile (the window starts anywhere inside a 32-key tile).  What the split
 // heuristics, the stream grid and the workspace are sized by.
 static inline int decode_visible_rows(const vattn_attn_params* p) {
-    const long w = (long)p->window_left_plus1 + DC_BN - 1;
+    const long w = (long)p->window_left_plus1 + (p->seqlen_q - 1) + DC_BN - 1;      // (multi-token form: the window of the entry's first query row)
     return (p->window_left_plus1 > 0 && w < p->seqlen_k) ? (int)w : p->seqlen_k;
 }
 
@@ -162,10 +163,12 @@ int pick_splits(const vattn_attn_params* p, int gblocks, long slots = 768) {
     return (int)pick;
 }
 
-// Head blocks per workgroup: two when the kv head serves more than 16 query heads (one pass over K/V for 32 heads).
-static inline int decode_nb(const vattn_attn_params* p) { return (p->h / p->h_k > 16 && !(p->variant & 128)) ? 2 : 1; }
+// MFMA columns a kv head carries: its G query heads — times the seqlen_q tokens of the multi-token form (decode_body.h, MT)
+static inline int decode_cols(const vattn_attn_params* p) { return p->h / p->h_k * p->seqlen_q; }
+// Head blocks per workgroup: two when the kv head serves more than 16 columns (one pass over K/V for 32 of them).
+static inline int decode_nb(const vattn_attn_params* p) { return (decode_cols(p) > 16 && !(p->variant & 128)) ? 2 : 1; }
 static inline int decode_groups(const vattn_attn_params* p) {
-    const int blocks = (p->h / p->h_k + 15) / 16;
+    const int blocks = (decode_cols(p) + 15) / 16;
     const int nb = decode_nb(p);
     return (blocks + nb - 1) / nb;
 }
@@ -181,7 +184,7 @@ static inline long decode_slots(const vattn_attn_params* p) {      // resident w
 // heuristics of rounds 1-3: ONE sequence (nothing to balance: its uniform split is the optimum and needs no plan prologue), GQA groups
 // wider than 16 heads, batches beyond DC_MAXB, explicit num_splits > 0, variant bit 19.  num_splits = -N forces N workgroups per group (tests, A/B).
 int stream_nwg(const vattn_attn_params* p) {
-    if (p->seqlen_q != 1 || p->split_items || p->num_splits > 0 || (p->variant & kVariantLegacyDecodePlan)) return 0;
+    if ((p->seqlen_q != 1 && !multitoken_form(p)) || p->split_items || p->num_splits > 0 || (p->variant & kVariantLegacyDecodePlan)) return 0;
     if (p->b > DC_MAXB || decode_groups(p) != 1) return 0;
     const long slots = decode_nb(p) == 2 ? 512 : 768;      // resident workgroups of decode_stream_kernel (its launch bounds)
     const long gps = p->h_k;
@@ -202,14 +205,21 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
 }
 
 // WIN: the sliding-window builds (decode_body.h) — taken iff the block carries a window, so a window-less call runs the kernels it always ran
-template <typename T, int HD, int NB, bool WIN> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg) {
+template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg) {
     if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
     if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
     const size_t smem = (size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2;
-    const int fused_append = (p->k_new && p->seqlen_knew == 1) ? 1 : 0;
+    const int fused_append = (!MT && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
     if (p->k_new && !fused_append) launch_append(p, st);
     const dim3 grid((unsigned)nwg, (unsigned)p->h_k), block(64 * DC_WAVES);
-    if constexpr (__is_same(T, __bf16)) {
+    if constexpr (MT) {
+        // multi-token form: the append is the launch above (rows land before the attention launch on the same stream), no fused rotation
+        hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, WIN, true>), grid, block, smem, st, *p, 1, 0);
+        hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB, true>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
+        return VATTN_K_OK;
+    } else if constexpr (__is_same(T, __bf16)) {
         // bf16 rotates through fp32 (no packed arithmetic): with the fused-RoPE path compiled in, decode_stream_kernel<bf16, 128, one head block> is
         // 12 registers over the 168 of three workgroups per CU and gets a scratch segment — 9 us per launch even when no rotation is asked for
         // (profiles/r06_decode_bf16_scratch.txt).  Two builds: without the path (what the reference's wrapper calls: no spill), and the one that
@@ -223,9 +233,9 @@ template <typename T, int HD, int NB, bool WIN> int launch_decode_stream(const v
     return VATTN_K_OK;
 }
 
-template <typename T, int HD, int NB, bool WIN> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st) {
+template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st) {
     constexpr int W = DC_WAVES;
-    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN>(p, st, nwg);
+    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT>(p, st, nwg);
     const int groups = decode_groups(p);
     const bool planned = p->split_items != nullptr;
     if (planned && (!p->split_seq || p->num_split_items <= 0)) return fail(VATTN_K_ERR_INVALID, "split_items needs split_seq and num_split_items");
@@ -238,20 +248,25 @@ template <typename T, int HD, int NB, bool WIN> int launch_decode_nb(const vattn
         grid = dim3((unsigned)(((w + 7) / 8) * 8 * groups));
     }
     const size_t smem = (size_t)W * 16 * HD * 4 + W * 16 * 4 * 2;   // merge area >= V staging (W x 8 KiB)
-    const int fused_append = (p->k_new && p->seqlen_knew == 1) ? 1 : 0;
-    if (p->k_new && !fused_append) launch_append(p, st);        // seqlen_knew > 1: separate append launch
+    const int fused_append = (!MT && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
+    if (p->k_new && !fused_append) launch_append(p, st);        // seqlen_knew > 1, multi-token form: separate append launch
     const vattn_attn_params& q = *p;
-    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN>), grid, block, smem, st, q, splits, groups, fused_append);
+    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT>), grid, block, smem, st, q, splits, groups, fused_append);
+    const int sq = MT ? p->seqlen_q : 1;
     if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, q);
-    else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, q, splits, 1);
+    else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * sq * p->h), dim3(128), 0, st, q, splits, sq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
     return VATTN_K_OK;
 }
 
+template <typename T, int HD, bool MT> int launch_decode_w(const vattn_attn_params* p, hipStream_t st) {
+    if (p->window_left_plus1 > 0) return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, true, MT>(p, st) : launch_decode_nb<T, HD, 1, true, MT>(p, st);
+    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, false, MT>(p, st) : launch_decode_nb<T, HD, 1, false, MT>(p, st);
+}
 template <typename T, int HD> int launch_decode_t(const vattn_attn_params* p, hipStream_t st) {
-    if (p->window_left_plus1 > 0) return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, true>(p, st) : launch_decode_nb<T, HD, 1, true>(p, st);
-    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, false>(p, st) : launch_decode_nb<T, HD, 1, false>(p, st);
+    if (p->seqlen_q == 1) return launch_decode_w<T, HD, false>(p, st);
+    return launch_decode_w<T, HD, true>(p, st);      // the multi-token form (the caller checked multitoken_form(p))
 }
 
 int launch_decode_form(const vattn_attn_params* p, hipStream_t st) {
@@ -367,7 +382,7 @@ size_t decode_workspace_bytes(const vattn_attn_params* p) {
     const int groups = decode_groups(p);
     const int splits = pick_splits(p, groups, decode_slots(p));
     if (splits <= 1) return 0;
-    return (size_t)splits * p->b * p->h * (p->d + 1) * sizeof(float);
+    return (size_t)splits * p->b * p->seqlen_q * p->h * (p->d + 1) * sizeof(float);      // (seqlen_q rows per entry in the multi-token form)
 }
 
 }  // namespace vattn_k

@@ -15,6 +15,11 @@ Supported: left >= 0 with right = 0 after those rules (and left < 0, right < 0: 
 reaches to the RIGHT of the diagonal (non-causal) raises NotImplementedError.  The kernels never read a key
 or value row below the first tile the window touches (include/vattn_kernels.h, "no-read contract").
 
+Multi-token decode: q [B, 2..8, Hq, D] with seqlen_q * (Hq / Hkv) <= 64 — the verify step of speculative decoding / multi-token
+prediction — runs on the split-KV decode kernels with no new argument (include/vattn_kernels.h, "multi-token form"): the rows of
+`k` / `v` are appended at cache_seqlens, then row t attends keys j <= Lk - Sq + t (causal) like any bottom-right-aligned call.  Works
+under graph capture like decode.  `_variant` with an explicit prefill tiling, num_splits > 0 or a rotary table keep the prefill kernels.
+
 Rotary embedding (`rotary_cos` / `rotary_sin` [seqlen_ro, rotary_dim/2], or `_rotary_cos_sin` = the
 reference model's own cos_sin_cache [max_position, rotary_dim]) is FUSED into the launch:
 q and the new k are rotated in registers, the rotated k is what lands in the cache.  NeoX pairing only
@@ -273,24 +278,28 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     p.softmax_scale = float(softmax_scale)
     p.variant = int(_variant)
     p.split_reserved = _STREAM_SWITCH
+    if rot is not None:
+        p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
+    # A few query rows per entry (the verify step of speculative decoding): the library runs them on the split-KV decode kernels (the
+    # multi-token form, include/vattn_kernels.h).  ITS gate decides — the library's plan description says which form the block takes — and the host work that only serves the prefill kernels (page-manager lengths, work lists) is skipped.
+    # (seqlen_q <= 8 is only the cheap necessary condition that keeps long prefill calls from paying for the question.)
+    multitoken = 1 < Sq <= 8 and D in (64, 128) and not K.needs_lab(p.variant) and K.describe(p)["form"] == 1      # (the lab library has no such form)
     # Prefill form WITHOUT any host-side length (the reference's own call: vattention_flashattention_wrapper.py:159-166 passes the slot's
     # whole row-block and `cache_seqlens` as a device tensor): the `vattention` drop-in was told every slot's length of this iteration in
     # step_async(seq_lens) — resolve the row-block's address to its slot and take the length from there.  No device-to-host copy, no
     # extra argument; a tensor that is not one of the page manager's leaves the view's row count as the bound (FlashAttention's own rule).
     klens = _cache_seqlens_host
-    if USE_PAGE_MANAGER_LENGTHS and Sq > 1 and hint == 0 and klens is None and cache_seqlens is not None and cache_batch_idx is None and k is None:
+    if USE_PAGE_MANAGER_LENGTHS and Sq > 1 and not multitoken and hint == 0 and klens is None and cache_seqlens is not None and cache_batch_idx is None and k is None:
         klens = _lengths_from_page_manager(k_cache, B)
         if klens is not None:
             hint = max(klens)
             counters["lengths_from_page_manager"] += 1
     p.max_seqlen_k_hint = min(hint, Sk + Sn) if hint > 0 else 0
-    if rot is not None:
-        p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
     plan = None
     # (a sliding window takes the default launch: its key walks are short and equal, the planners answer 0 for it and the library refuses
     # a list or host items beside one — include/vattn_kernels.h)
     windowed = p.window_left_plus1 > 0
-    if Sq > 1 and D == 128 and num_splits == 0 and k is None and not _capture_active() and not windowed:
+    if Sq > 1 and not multitoken and D == 128 and num_splits == 0 and k is None and not _capture_active() and not windowed:
         # prefill form: a work list for underfilled / unbalanced grids.  `_pf_plan`: a plan object built earlier for the same lengths
         # (this package's wrapper: one per iteration), else built here — and kept, keyed on the shapes and lengths: the L layers of an
         # iteration issue the same call — from the host-side lengths when there are any (_cache_seqlens_host, or the page manager's).
@@ -302,7 +311,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         if plan is not None:
             plan.attach(p)
             counters["work_list_attached"] += plan.t is not None
-    if Sq > 1:
+    if multitoken:
+        counters["multitoken_decode_calls"] += 1
+    elif Sq > 1:
         counters["prefill_calls"] += 1
     if _cache_seqlens_host is not None and Sq == 1 and B > 1 and num_splits == 0 and not windowed and not torch.cuda.is_current_stream_capturing():
         # (the plan's tables travel by a host-to-device copy: not while the stream is being captured into a graph — the uniform split then)
@@ -339,7 +350,7 @@ _plan_cache = {}      # (shapes, lengths, device, stream) -> _PrefillPlan; a few
 # with other lengths in between gets plans sized for the wrong lengths; False switches the lookup off (the view's row count then bounds
 # the plan, FlashAttention's own rule).
 USE_PAGE_MANAGER_LENGTHS = True
-counters = {"prefill_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
+counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
 
 
 def _cached_prefill_plan(p, klens, dev):
