@@ -222,6 +222,44 @@ int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
  * below align_down(first key visible to the entry's FIRST query row, 32). */
 int vattn_flash_attn_with_kvcache(const vattn_attn_params* p, void* stream);
 
+/* TREE-MASKED MULTI-TOKEN FORM (verifying a draft TREE — Medusa, EAGLE, SpecInfer — in one pass over the cache: a node sees its ancestors,
+ * not its siblings).  The multi-token form above with the causal rule among the draft rows replaced by a caller-given bit mask.  The mask
+ * travels BESIDE the parameter block — vattn_attn_params and VATTN_KERNELS_ABI are unchanged — as an extra argument of builds of the decode
+ * kernels of their own; every other kernel is what it was.
+ * MASK: tree_mask is DEVICE memory, uint32[b * seqlen_q], one word per (entry, query token); only the low seqlen_q bits are read; the
+ * host never dereferences it.  VISIBILITY: with Lk = cache_seqlens[b] + seqlen_knew visible keys (clamped to the view as everywhere) and
+ * base = Lk - seqlen_q, query token t of entry b sees every key j < base (the committed context) and draft key base + s iff bit s of
+ * tree_mask[b * seqlen_q + t] is set and base + s >= 0.  is_causal is ignored.  Any bit pattern is legal: no topological order and no self
+ * bit are required; a row without a visible key gives 0 and LSE +inf.  out, softmax_lse, strides and cache_batch_idx as in the multi-token
+ * form; k_new / v_new are appended by the same launch in front of the attention launch, bit-exact.  A chain is mask word t =
+ * (2 << t) - 1 (the causal multi-token call), all ones the non-causal one — equal to those calls up to the order of the fp32 sums.
+ * GATE: tree_mask == NULL delegates to vattn_flash_attn_with_kvcache(p, stream), unchanged.  Otherwise the block must take the multi-token
+ * form (its gate above: 2 <= seqlen_q <= 8, seqlen_q * G <= 64, no q_lens / pf_items / split_items / rotary_cos_sin, tiling bits zero,
+ * num_splits <= 0, the product library), else VATTN_K_ERR_UNSUPPORTED with a message that names the rule; window_left_plus1 > 0 beside a
+ * mask is VATTN_K_ERR_INVALID (a tree node's position is its depth, not its index: an index-based window would be wrong).
+ * vattn_tree_attn_workspace_bytes and vattn_tree_attn_plan_describe (form 1) answer what the multi-token call of the same block gets: the
+ * same planners, grids and workspace, nothing is tuned apart.  CONTRACT: no K/V load at or beyond Lk.  Draft keys a row must not see ARE
+ * loaded (they are other rows' keys) and masked before the softmax: they must hold finite-or-not data like any visible row, never sit on
+ * unmapped pages.  The keys that columns disagree about lie in at most two 32-key tiles at the tail; only those take the masked path. */
+int vattn_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_t* tree_mask, void* stream);
+size_t vattn_tree_attn_workspace_bytes(const vattn_attn_params* p);
+int vattn_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
+
+/* Compaction of the ACCEPTED path behind a tree-masked verify call, so that the virtually contiguous cache is contiguous again: for entry
+ * b (cache slot cache_batch_idx[b], identity if NULL) and i < keep_cnt[b], row row0[b] + i receives row row0[b] + keep_idx[b * n_draft + i],
+ * for K and V and all h_k kv heads.  keep_idx is strictly ascending per entry (so keep_idx[i] >= i; an index that is not is skipped).  In
+ * place and race-free: a thread owns one 16-byte chunk column, reads that chunk of all kept rows into registers, then stores them.  No
+ * other byte of the cache is written; rows at or past row0 + keep_cnt keep their contents.  The caller guarantees that rows
+ * [row0, row0 + n_draft) lie inside the cache view.  All index arrays are DEVICE int32.  Limits: n_draft <= 8, 2-byte dtypes
+ * (VATTN_DTYPE_*), d 64 / 128, strides multiples of 8 elements — anything else is VATTN_K_ERR_UNSUPPORTED. */
+int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
+                          int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride,
+                          const int32_t* row0,            /* device int32[b]: first draft row of each entry */
+                          const int32_t* cache_batch_idx, /* or NULL */
+                          const int32_t* keep_idx,        /* device int32[b * n_draft], strictly ascending per entry */
+                          const int32_t* keep_cnt,        /* device int32[b], 0..n_draft */
+                          int32_t b, int32_t n_draft, int32_t h_k, int32_t d, int32_t dtype, void* stream);
+
 /* Fused prefill || decode for a hybrid batch (replaces the reference's POD-Attention entry point
  * /root/reference/pod_attn/pod_attn/flash_attn_interface.py true_fused_attn_with_kvcache, call site
  * /root/reference/sarathi-lean/sarathi/model_executor/attention/vattention_flashattention_pod_wrapper.py:121-203): ONE launch of

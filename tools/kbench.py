@@ -2,7 +2,8 @@
 """Kernel microbenchmark (GPU): times the attention kernels through the C ABI with HIP events
 (vattn_time_attn) on the shapes of BASELINE.md §3 and prints TFLOP/s / GB/s against the rooflines.
 usage: python tools/kbench.py [prefill] [decode] [--variant N]
-       python tools/kbench.py multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base LIB] [--bf16]   (the multi-token decode form)"""
+       python tools/kbench.py multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base LIB] [--bf16] [--tree]   (the multi-token decode form;
+                                                                          --tree: the tree-masked entry with a chain mask beside the causal call)"""
 import ctypes as C
 import os
 import sys
@@ -171,7 +172,10 @@ def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
     """The multi-token decode call (q [B, sq, Hq, 128] against `ctx` cached tokens, the sq new rows appended) on caches that ROTATE (as
     --rotate: the Infinity Cache serves no repeat): this tree, the one-token decode step of the same batch, the prefill form of the same
     call (variant 8: what answered it before the form existed), the call and the one-token step WITHOUT k / v (same visible lengths, no
-    append) and — with --base PATH, a library built from another commit (tools/build_base.py) — that library's default launch of the same block.  ragged: lengths spread over [ctx / 8, ctx]."""
+    append) and — with --base PATH, a library built from another commit (tools/build_base.py) — that library's default launch of the same block.  ragged: lengths spread over [ctx / 8, ctx].
+    --tree (TREE): only the causal call and, beside it, the same block through vattn_tree_attn_with_kvcache with a CHAIN mask (the same visibility: what
+    the mask costs); for sq = 7 also the 7-node, 3-leaf tree 0-1-{3,4}, 0-2-5-6 in ONE call against the three per-path causal calls (3, 3 and
+    4 rows) that verify it without the tree form."""
     torch.manual_seed(0)
     slots = B
     by1 = B * 2.0 * ctx * Hkv * 128 * 2
@@ -183,7 +187,7 @@ def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
     st = torch.cuda.current_stream().cuda_stream
     libs = [("this tree", K.klib())] + ([("base", K._bind(C.CDLL(base_path)))] if base_path else [])
 
-    def run(label, lib, n, variant, append=True):
+    def run(label, lib, n, variant, append=True, mask_words=None):
         q = torch.randn(B, n, Hq, 128, device=DEV, dtype=DTYPE)
         kn, vn = torch.randn(B, n, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, n, Hkv, 128, device=DEV, dtype=DTYPE)
         ps = []
@@ -196,24 +200,37 @@ def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
             p.workspace = w.data_ptr()
             ps.append((p, keep, w))
         d = K.describe(ps[0][0], lib)
+        call = lib.vattn_flash_attn_with_kvcache
+        if mask_words is not None:          # the tree-masked entry point: the same block, the mask beside it
+            mask = torch.tensor(mask_words, dtype=torch.int32, device=DEV).expand(B, n).contiguous()
+            call = lambda pp, st_: lib.vattn_tree_attn_with_kvcache(pp, mask.data_ptr(), st_)
         best = []
         for _rep in range(3):
             for pp, _k, _w in ps:
-                if lib.vattn_flash_attn_with_kvcache(C.byref(pp), st) != 0:
+                if call(C.byref(pp), st) != 0:
                     raise RuntimeError(K.last_error(lib))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             iters = max(2, 40 // R + 1)
             e0.record()
             for _ in range(iters):
                 for pp, _k, _w in ps:
-                    lib.vattn_flash_attn_with_kvcache(C.byref(pp), st)
+                    call(C.byref(pp), st)
             e1.record()
             torch.cuda.synchronize()
             best.append(e0.elapsed_time(e1) / (iters * R) * 1e3)
         print("  %-34s form %d path %d tiling %d wg %5d : %8.1f us  (3 runs: %s)" % (label, d["form"], d["path"], d["tiling"], d["workgroups"], min(best),
                                                                                   " ".join("%.1f" % x for x in best)), flush=True)
+        return min(best)
     print("== multi-token decode B=%d sq=%d %d/%d heads ctx=%d%s, %s, D=128, %d rotating caches ==" % (
         B, sq, Hq, Hkv, ctx, " ragged" if ragged else "", "bf16" if DTYPE == torch.bfloat16 else "fp16", R), flush=True)
+    if TREE:
+        run("this tree: the call (causal)", K.klib(), sq, 0)
+        run("this tree: tree entry, chain mask", K.klib(), sq, 0, mask_words=[(2 << t) - 1 for t in range(sq)])
+        if sq == 7:
+            one = run("this tree: tree entry, 3-leaf tree", K.klib(), 7, 0, mask_words=[0b1, 0b11, 0b101, 0b1011, 0b10011, 0b100101, 0b1100101])
+            t3, t4 = run("this tree: causal call, 3-node path", K.klib(), 3, 0), run("this tree: causal call, 4-node path", K.klib(), 4, 0)
+            print("  one tree call %.1f us vs the three per-path calls (3 + 3 + 4 rows) %.1f us: %.2fx" % (one, 2 * t3 + t4, (2 * t3 + t4) / one), flush=True)
+        return
     for name, lib in libs:
         run("%s: the call (default plan)" % name, lib, sq, 0)
     run("this tree: prefill form (variant 8)", K.klib(), sq, 8)
@@ -234,6 +251,7 @@ MEGA = 1
 DTYPE = torch.float16
 SPLITS = (0,)
 PF_SPLITS = 0
+TREE = False
 
 if __name__ == "__main__":
     variant = 0
@@ -263,6 +281,7 @@ if __name__ == "__main__":
     if "multitoken" in sys.argv:
         # multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base build/base/libvattn_amd.so] [--bf16]
         base = sys.argv[sys.argv.index("--base") + 1] if "--base" in sys.argv else None
+        TREE = "--tree" in sys.argv
         shapes = []
         for i, a in enumerate(sys.argv):
             if a == "--mt":

@@ -69,3 +69,37 @@ def rotary_embedding(positions: torch.Tensor, query: torch.Tensor, key: torch.Te
                                          K.current_stream_ptr(query.device))
     if rc != 0:
         raise RuntimeError(K.last_error())
+
+
+def keep_rows(k_cache: torch.Tensor, v_cache: torch.Tensor, row0: torch.Tensor, keep_idx: torch.Tensor, keep_cnt: torch.Tensor,
+              cache_batch_idx=None) -> None:
+    """MI355X extension (include/vattn_kernels.h, vattn_cache_keep_rows): compaction of the accepted draft rows behind a tree-masked verify
+    call (flash_attn.flash_attn_tree_with_kvcache), in place, on the current stream.  Caches [Bc, rows, Hkv, D] (any strided view with a
+    contiguous last dimension); row0 int32 [B]: first draft row of each entry (the cache_seqlens of the verify call); keep_idx int32
+    [B, n_draft <= 8]: the draft rows to keep, strictly ascending per entry; keep_cnt int32 [B]: how many of them.  Row row0 + i of slot
+    cache_batch_idx[b] receives row row0 + keep_idx[b, i] for i < keep_cnt[b]; nothing else is written.  No host synchronisation."""
+    ts = (k_cache, v_cache, row0, keep_idx, keep_cnt, cache_batch_idx)
+    if not all(t.is_cuda for t in ts if t is not None):
+        raise RuntimeError("vattention_amd.cache_ops: tensors must live on the GPU (there is no CPU path)")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.dtype != v_cache.dtype or k_cache.stride(-1) != 1 or v_cache.stride(-1) != 1:
+        raise RuntimeError("keep_rows expects k_cache and v_cache [slots, rows, kv heads, head_size] of one shape and dtype, last dimension contiguous")
+    if keep_idx.dim() != 2:
+        raise RuntimeError("keep_idx must be [batch, n_draft]")
+    B, n_draft = keep_idx.shape
+    for t, name in ((row0, "row0"), (keep_idx, "keep_idx"), (keep_cnt, "keep_cnt"), (cache_batch_idx, "cache_batch_idx")):
+        if t is not None and t.dtype != torch.int32:
+            raise RuntimeError(name + " must have dtype int32")
+    if row0.shape != (B,) or keep_cnt.shape != (B,) or (cache_batch_idx is not None and cache_batch_idx.shape != (B,)):
+        raise RuntimeError("row0, keep_cnt and cache_batch_idx must have one entry per row of keep_idx")
+    if cache_batch_idx is None and k_cache.shape[0] < B:
+        raise RuntimeError("batch size of the cache is smaller than the batch size of keep_idx")
+    if B == 0:
+        return
+    row0, keep_idx, keep_cnt = row0.contiguous(), keep_idx.contiguous(), keep_cnt.contiguous()
+    cbi = cache_batch_idx.contiguous() if cache_batch_idx is not None else None
+    rc = K.klib().vattn_cache_keep_rows(k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+                                        v_cache.stride(0), v_cache.stride(1), v_cache.stride(2), row0.data_ptr(),
+                                        cbi.data_ptr() if cbi is not None else None, keep_idx.data_ptr(), keep_cnt.data_ptr(), B, n_draft,
+                                        k_cache.shape[2], k_cache.shape[3], K.dtype_code(k_cache.dtype), K.current_stream_ptr(k_cache.device))
+    if rc != 0:
+        raise (NotImplementedError if rc == -10 else RuntimeError)(K.last_error())

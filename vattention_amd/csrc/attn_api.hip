@@ -287,6 +287,19 @@ static int32_t window_plan_none(int32_t* counts_out, int n) {
     return 0;
 }
 
+// Why a block is outside the gate of the tree-masked form — multitoken_form (attn_common.h) rule by rule — or NULL when it passes
+static const char* tree_gate_reason(const vattn_attn_params* p) {
+    if (kLab) return "the measurement build has no tree-masked kernels (use libvattn_amd.so)";
+    if (p->seqlen_q < 2 || p->seqlen_q > 8) return "a tree mask needs 2 <= seqlen_q <= 8 (one mask word of 8 bits per query token)";
+    if (p->h_k <= 0 || p->h < p->h_k || (long)p->seqlen_q * (p->h / p->h_k) > 64) return "a tree mask needs seqlen_q * (h / h_k) <= 64 (token, head) columns per kv head";
+    if (p->q_lens || p->pf_items || p->split_items) return "a tree mask cannot be combined with q_lens / pf_items / split_items";
+    if (p->rotary_cos_sin) return "a tree mask cannot be combined with fused rotary embedding (rotary_cos_sin): rotate q and k first";
+    if ((p->variant >> 1) & 7) return "a tree mask needs the default tiling (variant bits 1-3 zero)";
+    if (p->num_splits > 0) return "a tree mask needs num_splits <= 0";
+    return multitoken_form(p) ? nullptr : "the block does not take the multi-token form";
+}
+static const char* kTreeWindow = "a tree mask cannot be combined with a sliding window (window_left_plus1 > 0): a node's position is its depth, not its index";
+
 }  // namespace vattn_k
 
 using namespace vattn_k;
@@ -307,6 +320,34 @@ int vattn_flash_attn_with_kvcache(const vattn_attn_params* p, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
     return decode_form(p) ? launch_decode_form(p, st) : launch_prefill_form(p, st);
+}
+
+int vattn_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_t* tree_mask, void* stream) {
+    if (!tree_mask) return vattn_flash_attn_with_kvcache(p, stream);
+    if (!abi_ok(p)) return validate(p);
+    if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);      // (before validate: is_causal is ignored in this form)
+    int rc = validate(p);
+    if (rc) return rc;
+    if (const char* why = tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
+#ifndef VATTN_LAB
+    return launch_tree_form(p, tree_mask, (hipStream_t)stream);
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
+}
+
+// The tree-masked call runs the multi-token launch of the same block on other builds of the same kernels: same planners, same answers.
+size_t vattn_tree_attn_workspace_bytes(const vattn_attn_params* p) {
+    if (!abi_ok(p) || p->window_left_plus1 > 0 || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || tree_gate_reason(p)) return 0;
+    return vattn_attn_workspace_bytes(p);
+}
+
+int vattn_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
+    if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
+    if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);
+    if (const char* why = tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    return vattn_attn_plan_describe(p, out);
 }
 
 int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {

@@ -282,6 +282,7 @@ void launch_prefill64(const vattn_attn_params* p, hipStream_t st, int nsplit, in
 #endif
 int* merge_counters(hipStream_t st, size_t n_ints);                      // attn_api.hip: zeroed per-(device, stream) counters, NULL while capturing
 int launch_decode_form(const vattn_attn_params* p, hipStream_t st);     // decode_kernels.hip (decode_form(p): seqlen_q == 1, or the multi-token form)
+int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st);   // decode_kernels.hip (product library only): the tree-masked multi-token form
 size_t decode_workspace_bytes(const vattn_attn_params* p);
 int decode_plan(const vattn_attn_params* p, const int32_t* lens, vattn_decode_item* items, int cap, int32_t* seq);   // decode_kernels.hip
 void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out);   // prefill_kernels.hip

@@ -142,6 +142,43 @@ __global__ void append_kv_kernel(vattn_attn_params p) {
     }
 }
 
+// vattn_cache_keep_rows (include/vattn_kernels.h): compaction of the accepted draft rows behind a tree-masked verify call, in place.  One
+// thread per (entry, K or V, kv head, 16-byte chunk): it reads ITS chunk of the kept rows (at most 8) into registers, then stores them to
+// rows row0 .. row0 + cnt - 1 — every byte is read and written by one thread only, reads before writes: no race, whatever the overlap of
+// source and destination rows.  An index outside [i, n_draft) breaks the caller's contract (strictly ascending): that row is left alone.
+constexpr int KEEP_MAX = 8;
+__global__ void cache_keep_rows_kernel(uint16_t* k_cache, uint16_t* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
+                                       int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride, const int32_t* row0,
+                                       const int32_t* cache_batch_idx, const int32_t* keep_idx, const int32_t* keep_cnt, int b_total, int n_draft,
+                                       int h_k, int cpr) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b_total * 2 * h_k * cpr) return;
+    const int c = i % cpr;
+    const int hk = (i / cpr) % h_k;
+    const int is_v = (i / (cpr * h_k)) & 1;
+    const int b = i / (cpr * h_k * 2);
+    const int slot = cache_batch_idx ? cache_batch_idx[b] : b;
+    const int cnt = min(max(keep_cnt[b], 0), n_draft);
+    const int64_t row_stride = is_v ? v_row_stride : k_row_stride;
+    uint16_t* base = is_v ? v_cache + (int64_t)slot * v_batch_stride + (int64_t)hk * v_head_stride
+                          : k_cache + (int64_t)slot * k_batch_stride + (int64_t)hk * k_head_stride;
+    base += (int64_t)row0[b] * row_stride + c * 8;
+    uint4 rows[KEEP_MAX];
+    bool ok[KEEP_MAX];
+#pragma unroll
+    for (int j = 0; j < KEEP_MAX; j++) {
+        ok[j] = false;
+        if (j < cnt) {
+            const int src = keep_idx[b * n_draft + j];
+            ok[j] = src >= j && src < n_draft;
+            if (ok[j]) rows[j] = *(const uint4*)(base + (int64_t)src * row_stride);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < KEEP_MAX; j++)
+        if (ok[j]) *(uint4*)(base + (int64_t)j * row_stride) = rows[j];
+}
+
 void launch_append(const vattn_attn_params* p, hipStream_t st) {
     const int total = p->seqlen_knew * p->h_k * (p->d / 8);
     dim3 grid((total + 255) / 256, p->b), block(256);
@@ -189,6 +226,27 @@ int vattn_cache_flat(const void* key, const void* value, void* k_cache, void* v_
         else
             return fail(VATTN_K_ERR_UNSUPPORTED, "cache_flat supports 2- and 4-byte element types");
     }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
+    return VATTN_K_OK;
+}
+
+int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
+                          int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride, const int32_t* row0,
+                          const int32_t* cache_batch_idx, const int32_t* keep_idx, const int32_t* keep_cnt, int32_t b, int32_t n_draft,
+                          int32_t h_k, int32_t d, int32_t dtype, void* stream) {
+    if (!k_cache || !v_cache || !row0 || !keep_idx || !keep_cnt) return fail(VATTN_K_ERR_INVALID, "null tensor pointer");
+    if (b <= 0 || h_k <= 0 || n_draft <= 0) return fail(VATTN_K_ERR_INVALID, "cache_keep_rows: batch size, kv heads and n_draft must be positive");
+    if (dtype != VATTN_DTYPE_F16 && dtype != VATTN_DTYPE_BF16) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows supports fp16 and bf16");
+    if (n_draft > KEEP_MAX) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows handles at most 8 draft rows per entry");
+    if (d != 64 && d != 128) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows supports head dimensions 64 and 128");
+    if (((k_batch_stride | k_row_stride | k_head_stride | v_batch_stride | v_row_stride | v_head_stride) & 7) || ((((uintptr_t)k_cache) | ((uintptr_t)v_cache)) & 15))
+        return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows needs 16-byte aligned rows (strides of 8 elements)");
+    const int64_t total = (int64_t)b * 2 * h_k * (d / 8);
+    if (total > 0x7fffffff) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows: batch too large");
+    hipLaunchKernelGGL(cache_keep_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint16_t*)k_cache, (uint16_t*)v_cache,
+                       k_batch_stride, k_row_stride, k_head_stride, v_batch_stride, v_row_stride, v_head_stride, row0, cache_batch_idx, keep_idx,
+                       keep_cnt, (int)b, (int)n_draft, (int)h_k, (int)(d / 8));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
     return VATTN_K_OK;

@@ -38,12 +38,20 @@ constexpr int DC_BN = 32;     // keys per wave tile
 // front) take the masked path, where every lane compares against ITS column's bounds; waves interleave tile by tile (or further apart),
 // so a wave owns at most one tile of each pair, and it is its last resp. first tile.  The first visible key of the ENTRY is token 0's
 // (tile0, the no-read contract).  No fused append, no fused rotation: the host launches the append first (launch_append).
-template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false>
+// TREE: the TREE-MASKED multi-token form (vattn_tree_attn_with_kvcache, include/vattn_kernels.h; MT builds without a window only) — the
+// seqlen_q query rows are the nodes of a draft tree whose K/V rows are the entry's last seqlen_q keys.  Token t sees every key below
+// base = Lk - seqlen_q and draft key base + s iff bit s of tree_mask[b * seqlen_q + t] is set; is_causal is ignored.  The per-column bounds
+// of the masked tail tiles become a per-column bit mask, loaded there; the steady-state loop is the MT one.  The mask pointer is a kernel
+// argument of these builds alone (tree_mask_arg): vattn_attn_params is frozen, and the other builds keep their argument lists.
+struct no_tree_mask {};
+template <bool TREE> using tree_mask_arg = std::conditional_t<TREE, const uint32_t*, no_tree_mask>;
+template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,
                                             const int item = -1, const int item_tb = 0, const int item_te = 0,
                                             const int st_mode = 0, const int st_slot = 0, const int st_lk = 0, const unsigned st_block = 0,
-                                            const int tstride = 1) {
+                                            const int tstride = 1, const uint32_t* tree_mask = nullptr) {
+    static_assert(!TREE || (MT && !WIN), "the tree mask belongs to the window-less multi-token builds");
     // st_mode != 0: a piece [item_tb, item_te) of the device-planned stream decomposition (decode_stream_kernel below).  Slot and visible
     // length come from the workgroup's plan (LDS) instead of two dependent global loads; st_mode 1 = the piece is the whole sequence: the
     // final rows are written; st_mode 2 = a partial, published as one record block at byte offset st_block of the workspace (16-byte
@@ -271,7 +279,25 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                     for (int r = 0; r < 4; r++)
                         if (k0 + 16 * kb + 4 * g4 + r >= Lk || (WIN && k0 + 16 * kb + 4 * g4 + r < w0)) s[nb][kb][r] = -INFINITY;
             }
-            if constexpr (MT) {
+            if constexpr (TREE) {
+                if (RAGGED) {
+                    // this lane's column: token t's mask word over the entry's last seqlen_q keys (bit s <-> key base + s; base < 0: the keys
+                    // below 0 do not exist, bit s still names key base + s) — loaded here, in the at most two masked tiles of a wave.
+                    // hide = ~(word & low seqlen_q bits): bit s set <-> draft key base + s is hidden, and every bit from seqlen_q on is
+                    // set: the keys at or beyond Lk.  Key k is masked iff k >= base and bit min(k - base, 31) of hide is set — selects, no branch
+                    const int t = min(((gb * NB + nb) * 16 + l15) / G, qoff);
+                    const unsigned hide = ~(tree_mask[(int64_t)b * p.seqlen_q + t] & ((1u << p.seqlen_q) - 1u));
+                    const int rel = k0 + 4 * g4 - (Lk - p.seqlen_q);           // key of slot (kb = 0, r = 0) relative to base
+#pragma unroll
+                    for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const int sft = rel + 16 * kb + r;
+                            const unsigned hidden = (hide >> (unsigned)min(max(sft, 0), 31)) & (sft >= 0 ? 1u : 0u);
+                            s[nb][kb][r] = hidden ? -INFINITY : s[nb][kb][r];
+                        }
+                }
+            } else if constexpr (MT) {
                 if (RAGGED) {
                     // this lane's column sees keys [lo, hi) — derived here, in the at most two masked tiles of a wave, instead of living
                     // in registers through the key walk
@@ -349,7 +375,9 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     if constexpr (MT) {
         // tail tiles: those that hold a key some column cannot see — keys from hi_0 = Lk - (seqlen_q - 1) on (causal), or the keys at or
         // beyond Lk of a ragged last tile.  seqlen_q - 1 < 32: at most the last two tiles; a wave's tiles are >= 4 apart: it owns at most one
-        const int mask_from = p.is_causal ? max(0, Lk - qoff) : Lk;
+        // TREE: from the first draft key, base = Lk - seqlen_q, on — even draft key 0 may be invisible to some row.  seqlen_q <= 8 < 32: still at
+        // most the last two tiles (t0 * 32 <= base and Lk <= base + 8 < (t0 + 2) * 32), and a wave still owns at most one of them
+        const int mask_from = TREE ? max(0, Lk - p.seqlen_q) : p.is_causal ? max(0, Lk - qoff) : Lk;
         const int t0 = mask_from / DC_BN, t1 = t0 + 1;
         const bool own0 = t0 <= last_tile && t0 >= first && t0 < tile_end && ((t0 - first) % wstep) == 0;
         const bool own1 = t1 <= last_tile && t1 >= first && t1 < tile_end && ((t1 - first) % wstep) == 0;
@@ -723,8 +751,10 @@ __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, 
 
 // nwg: workgroups per (kv head, group) = gridDim.x.  The partials are merged by decode_stream_combine_kernel in a second launch (merging
 // inside the launch, XCD-consecutive ranges, per-workgroup clock stamps, fair-share issue priority: tools/lab/csrc/decode_body_lab.h).
-template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false>
-__global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append) {
+template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false>
+__global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append, tree_mask_arg<TREE> tree_mask = {}) {
+    const uint32_t* tmask = nullptr;
+    if constexpr (TREE) tmask = tree_mask;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_plan[3 * DC_MAXB];                // stream mode: the plan, for the pieces after the first
     const int tid = threadIdx.x;
@@ -793,7 +823,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     for (;;) {
         const unsigned blk = stream_table_bytes(p.b) + (((unsigned)(w + b) * p.h_k + hk) * gblocks + gb) * RB;
         if (tb == 0 && hk == 0 && gb == 0 && tid == 0) stream_publish_seq(p, b, first_rec, cnt);      // (the owner of the sequence's first piece)
-        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk);
+        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT, TREE>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk, 1, tmask);
         if (geo.uniform || !next_piece(b + 1)) return;
         __syncthreads();                                 // the previous piece's in-workgroup merge is done with the LDS
     }
@@ -812,9 +842,11 @@ __global__ __launch_bounds__(256) void decode_stream_combine_kernel(vattn_attn_p
 
 // gblocks = head-block GROUPS per kv head (ceil(ceil(G/16) / NB)).  The partials of a split launch are merged by combine_kernel in a
 // second launch (the single-launch merges live in the lab copy).
-template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false>
-__global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append) {
+template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false, bool TREE = false>
+__global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append, tree_mask_arg<TREE> tree_mask = {}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t* tmask = nullptr;
+    if constexpr (TREE) tmask = tree_mask;
     int split, hk, gb, b;
     if (!MT && p.split_items != nullptr) {          // (host items: the one-token form only)
         // length-balanced plan: blockIdx.x = work item (a piece of ONE sequence), blockIdx.y = (kv head, head-block group)
@@ -842,8 +874,8 @@ __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB >
         gb = blockIdx.y % gblocks;
         b = blockIdx.z;
     }
-    decode_body<T, HD, USE_TR, NB, W, PF, MT ? 0 : -1, WIN, MT>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
-                                          (decode_striped(p) && num_splits > 1) ? num_splits : 1);
+    decode_body<T, HD, USE_TR, NB, W, PF, MT ? 0 : -1, WIN, MT, TREE>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
+                                          (decode_striped(p) && num_splits > 1) ? num_splits : 1, tmask);
 }
 
 }  // namespace vattn_k

@@ -205,7 +205,8 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
 }
 
 // WIN: the sliding-window builds (decode_body.h) — taken iff the block carries a window, so a window-less call runs the kernels it always ran
-template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg) {
+// TREE: the tree-masked builds of the multi-token form (decode_body.h) — the same plan, grid and workspace; the mask is their extra argument
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE = false> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const uint32_t* tree_mask = nullptr) {
     if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
     if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
     const size_t smem = (size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2;
@@ -214,7 +215,8 @@ template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_strea
     const dim3 grid((unsigned)nwg, (unsigned)p->h_k), block(64 * DC_WAVES);
     if constexpr (MT) {
         // multi-token form: the append is the launch above (rows land before the attention launch on the same stream), no fused rotation
-        hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, WIN, true>), grid, block, smem, st, *p, 1, 0);
+        if constexpr (TREE) hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, false, true, true>), grid, block, smem, st, *p, 1, 0, tree_mask);
+        else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, WIN, true>), grid, block, smem, st, *p, 1, 0);
         hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB, true>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
@@ -233,9 +235,9 @@ template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_strea
     return VATTN_K_OK;
 }
 
-template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st) {
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE = false> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask = nullptr) {
     constexpr int W = DC_WAVES;
-    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT>(p, st, nwg);
+    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT, TREE>(p, st, nwg, tree_mask);
     const int groups = decode_groups(p);
     const bool planned = p->split_items != nullptr;
     if (planned && (!p->split_seq || p->num_split_items <= 0)) return fail(VATTN_K_ERR_INVALID, "split_items needs split_seq and num_split_items");
@@ -251,7 +253,8 @@ template <typename T, int HD, int NB, bool WIN, bool MT> int launch_decode_nb(co
     const int fused_append = (!MT && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
     if (p->k_new && !fused_append) launch_append(p, st);        // seqlen_knew > 1, multi-token form: separate append launch
     const vattn_attn_params& q = *p;
-    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT>), grid, block, smem, st, q, splits, groups, fused_append);
+    if constexpr (TREE) hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, false, true, true>), grid, block, smem, st, q, splits, groups, fused_append, tree_mask);
+    else hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT>), grid, block, smem, st, q, splits, groups, fused_append);
     const int sq = MT ? p->seqlen_q : 1;
     if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, q);
     else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * sq * p->h), dim3(128), 0, st, q, splits, sq);
@@ -273,6 +276,17 @@ int launch_decode_form(const vattn_attn_params* p, hipStream_t st) {
     const bool f16 = p->dtype == VATTN_DTYPE_F16;
     if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64>(p, st) : launch_decode_t<__bf16, 64>(p, st);
     return f16 ? launch_decode_t<_Float16, 128>(p, st) : launch_decode_t<__bf16, 128>(p, st);
+}
+
+// vattn_tree_attn_with_kvcache (the caller checked multitoken_form(p) and that the block carries no window): the multi-token launch of
+// the same block — planners, grids, append, merges — on the TREE builds
+template <typename T, int HD> static int launch_tree_t(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) {
+    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, false, true, true>(p, st, tree_mask) : launch_decode_nb<T, HD, 1, false, true, true>(p, st, tree_mask);
+}
+int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) {
+    const bool f16 = p->dtype == VATTN_DTYPE_F16;
+    if (p->d == 64) return f16 ? launch_tree_t<_Float16, 64>(p, tree_mask, st) : launch_tree_t<__bf16, 64>(p, tree_mask, st);
+    return f16 ? launch_tree_t<_Float16, 128>(p, tree_mask, st) : launch_tree_t<__bf16, 128>(p, tree_mask, st);
 }
 
 // Length-balanced split of a ragged decode batch (include/vattn_kernels.h, vattn_decode_plan).  Every sequence is cut into pieces of at

@@ -20,6 +20,9 @@ prediction — runs on the split-KV decode kernels with no new argument (include
 `k` / `v` are appended at cache_seqlens, then row t attends keys j <= Lk - Sq + t (causal) like any bottom-right-aligned call.  Works
 under graph capture like decode.  `_variant` with an explicit prefill tiling, num_splits > 0 or a rotary table keep the prefill kernels.
 
+Tree-masked multi-token decode: `flash_attn_tree_with_kvcache` (below; not part of the reference's interface) verifies a draft TREE in
+the same single pass — the draft rows see each other through a caller-given bit mask instead of the causal rule.
+
 Rotary embedding (`rotary_cos` / `rotary_sin` [seqlen_ro, rotary_dim/2], or `_rotary_cos_sin` = the
 reference model's own cos_sin_cache [max_position, rotary_dim]) is FUSED into the launch:
 q and the new k are rotated in registers, the rotated k is what lands in the cache.  NeoX pairing only
@@ -329,6 +332,107 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     return (out, lse) if return_softmax_lse else out
 
 
+def _pack_tree_mask(tree_mask, B: int, Sq: int, dev) -> torch.Tensor:
+    """int32 [B, Sq] mask words (bit s of word t: query token t sees draft key s) from the accepted forms of `tree_mask`; on the device."""
+    if not isinstance(tree_mask, torch.Tensor) or not tree_mask.is_cuda:
+        raise RuntimeError("tree_mask must be a GPU tensor (it is read by the kernel, never by the host)")
+    if tree_mask.dtype == torch.bool:
+        if tree_mask.shape not in ((Sq, Sq), (B, Sq, Sq)):
+            raise RuntimeError("a bool tree_mask must be [seqlen_q, seqlen_q] or [batch, seqlen_q, seqlen_q]")
+        words = (tree_mask.to(torch.int32) << torch.arange(Sq, dtype=torch.int32, device=dev)).sum(dim=-1, dtype=torch.int32)
+        return words.expand(B, Sq).contiguous()
+    if tree_mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tree_mask.shape != (B, Sq):
+        raise RuntimeError("tree_mask must be int32 / uint32 [batch, seqlen_q] bit words or a bool [batch, seqlen_q, seqlen_q] / [seqlen_q, seqlen_q] tensor")
+    return tree_mask.contiguous()
+
+
+def _launch_tree(p, mask: torch.Tensor, dev, keep=()):
+    """_launch for the tree-masked entry point (vattn_tree_attn_with_kvcache): the product library only."""
+    lib = K.klib()
+    st = K.current_stream_ptr(dev)
+    need = lib.vattn_tree_attn_workspace_bytes(C.byref(p))      # (0 for a block outside the gate: the call below refuses it)
+    if need:
+        p.workspace = _workspace(need, dev, st).data_ptr()
+    rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
+    if rc == -10:
+        raise NotImplementedError(K.last_error(lib))
+    if rc != 0:
+        raise RuntimeError(K.last_error(lib))
+
+
+def flash_attn_tree_with_kvcache(q, k_cache, v_cache, tree_mask, k=None, v=None, cache_seqlens: Optional[Union[int, torch.Tensor]] = None,
+                                 cache_batch_idx: Optional[torch.Tensor] = None, softmax_scale=None, return_softmax_lse=False, out=None,
+                                 _num_splits: int = 0):
+    """MI355X extension (include/vattn_kernels.h, "tree-masked multi-token form"): verify a draft TREE of Sq = 2..8 nodes per entry in ONE pass
+    over the cache.  q [B, Sq, Hq, D] with Sq * (Hq / Hkv) <= 64; the nodes' K/V rows are the entry's last Sq keys — `k` / `v` [B, Sq, Hkv, D]
+    appended at cache_seqlens first, or rows already in the cache.  With Lk = cache_seqlens + rows of k and base = Lk - Sq, node t sees every
+    key below base and draft key base + s iff tree_mask says so: an int32 / uint32 [B, Sq] tensor of bit words (bit s of word t), or a bool
+    [B, Sq, Sq] / [Sq, Sq] tensor ([.., t, s]; packed on the device, broadcast over the batch).  Any pattern is legal; a node that sees no
+    key gives 0 (LSE +inf).  No causal flag (the mask is the rule), no window, no rotary: calls outside the gate raise NotImplementedError
+    naming the rule.  `_num_splits` < 0: the decode kernels' forced grids (tests, A/B).  Works under graph capture like decode.  Afterwards `cache_ops.keep_rows` makes the accepted path contiguous."""
+    _check_cuda(q, k_cache, v_cache, k, v)
+    assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
+    assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
+    mc = lambda x: x.contiguous() if x is not None and x.stride(-1) != 1 else x
+    q, k, v = mc(q), mc(k), mc(v)
+    B, Sq, Hq, D = q.shape
+    Bc, Sk, Hkv, Dk = k_cache.shape
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise RuntimeError("query, key and value must have the same dtype")
+    dev = q.device
+    if not 2 <= Sq <= 8:
+        raise NotImplementedError("a tree mask needs 2 <= seqlen_q <= 8 (one mask word of 8 bits per query token); got %d" % Sq)
+    mask = _pack_tree_mask(tree_mask, B, Sq, dev)
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=dev)
+    if cache_seqlens is not None:
+        if cache_seqlens.dtype != torch.int32:
+            raise RuntimeError("seqlens_k must have dtype int32")
+        cache_seqlens = cache_seqlens.contiguous()
+        assert cache_seqlens.shape == (B,)
+    if cache_batch_idx is not None:
+        if cache_batch_idx.dtype != torch.int32:
+            raise RuntimeError("cache_batch_idx must have dtype int32")
+        cache_batch_idx = cache_batch_idx.contiguous()
+    elif Bc < B:
+        raise RuntimeError("batch size of the cache is smaller than the batch size of q")
+    Sn = 0
+    if k is not None:
+        if v is None:
+            raise RuntimeError("If key is supplied, value must also be passed in")
+        if cache_seqlens is None:
+            raise RuntimeError("If key is supplied, seqlens_k must also be passed in")
+        Sn = k.shape[1]
+        if Sn > Sk:
+            raise RuntimeError(APPEND_ERR)
+        assert k.shape == (B, Sn, Hkv, D) and v.shape == (B, Sn, Hkv, D)
+    if out is None:
+        out = torch.empty_like(q)
+    elif out.dtype != q.dtype or out.shape != q.shape or out.stride(-1) != 1:
+        raise RuntimeError("Output tensor must have the shape and dtype of q and a contiguous last dimension")
+    lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_softmax_lse else None
+    p = K.AttnParams()
+    p.q, p.out = q.data_ptr(), out.data_ptr()
+    p.q_batch_stride, p.q_row_stride, p.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
+    p.o_batch_stride, p.o_row_stride, p.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
+    _set_cache(p, k_cache, v_cache)
+    if k is not None:
+        p.k_new, p.v_new = k.data_ptr(), v.data_ptr()
+        p.knew_batch_stride, p.knew_row_stride, p.knew_head_stride = k.stride(0), k.stride(1), k.stride(2)
+        p.vnew_batch_stride, p.vnew_row_stride, p.vnew_head_stride = v.stride(0), v.stride(1), v.stride(2)
+    p.cache_seqlens = cache_seqlens.data_ptr() if cache_seqlens is not None else None
+    p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
+    p.softmax_lse = lse.data_ptr() if lse is not None else None
+    p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, Sq, Sk, Sn, Hq, Hkv, D
+    p.dtype = K.dtype_code(q.dtype)
+    p.num_splits = int(_num_splits)
+    p.softmax_scale = float(D ** (-0.5) if softmax_scale is None else softmax_scale)
+    p.split_reserved = _STREAM_SWITCH
+    _launch_tree(p, mask, dev, keep=(q, k, v, k_cache, v_cache, cache_seqlens, cache_batch_idx, out, lse, mask))
+    counters["tree_decode_calls"] += 1
+    return (out, lse) if return_softmax_lse else out
+
+
 def _lengths_from_page_manager(k_cache, B: int):
     """Visible tokens of the B row-blocks of `k_cache` according to the page manager's last step (vattention.resolve_view), or None."""
     from . import vattention as _va
@@ -350,7 +454,7 @@ _plan_cache = {}      # (shapes, lengths, device, stream) -> _PrefillPlan; a few
 # with other lengths in between gets plans sized for the wrong lengths; False switches the lookup off (the view's row count then bounds
 # the plan, FlashAttention's own rule).
 USE_PAGE_MANAGER_LENGTHS = True
-counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
+counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
 
 
 def _cached_prefill_plan(p, klens, dev):

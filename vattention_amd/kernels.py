@@ -97,6 +97,14 @@ def _bind(lib):
                                           C.POINTER(i32), i32, C.POINTER(i32)]
     lib.vattn_attn_plan_describe.restype = i32
     lib.vattn_attn_plan_describe.argtypes = [C.POINTER(AttnParams), C.POINTER(PlanDesc)]
+    lib.vattn_tree_attn_with_kvcache.restype = i32
+    lib.vattn_tree_attn_with_kvcache.argtypes = [C.POINTER(AttnParams), vp, vp]
+    lib.vattn_tree_attn_workspace_bytes.restype = C.c_size_t
+    lib.vattn_tree_attn_workspace_bytes.argtypes = [C.POINTER(AttnParams)]
+    lib.vattn_tree_attn_plan_describe.restype = i32
+    lib.vattn_tree_attn_plan_describe.argtypes = [C.POINTER(AttnParams), C.POINTER(PlanDesc)]
+    lib.vattn_cache_keep_rows.restype = i32
+    lib.vattn_cache_keep_rows.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.vattn_decode_plan.restype = i32
     lib.vattn_decode_plan.argtypes = [C.POINTER(AttnParams), C.POINTER(i32), C.POINTER(DecodeItem), i32, C.POINTER(i32)]
     return lib
@@ -136,6 +144,16 @@ def describe(p, lib=None) -> dict:
     """The launch plan of parameter block `p` (vattn_attn_plan_describe): pure host arithmetic."""
     d = PlanDesc()
     rc = (lib or klib()).vattn_attn_plan_describe(C.byref(p), C.byref(d))
+    if rc != 0:
+        raise RuntimeError(last_error(lib))
+    return {n: int(getattr(d, n)) for n, _ in d._fields_}
+
+
+def describe_tree(p, lib=None) -> dict:
+    """The launch plan of the tree-masked call of block `p` (vattn_tree_attn_plan_describe): the multi-token call's, or an error naming
+    the rule of the gate the block breaks."""
+    d = PlanDesc()
+    rc = (lib or klib()).vattn_tree_attn_plan_describe(C.byref(p), C.byref(d))
     if rc != 0:
         raise RuntimeError(last_error(lib))
     return {n: int(getattr(d, n)) for n, _ in d._fields_}
