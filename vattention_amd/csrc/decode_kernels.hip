@@ -204,90 +204,91 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
     return stream_table_bytes(p->b) + (size_t)(nwg + p->b) * p->h_k * rf * sizeof(float);      // (first record, count) per sequence, then the records
 }
 
-// WIN: the sliding-window builds (decode_body.h) — taken iff the block carries a window, so a window-less call runs the kernels it always ran
-// TREE: the tree-masked builds of the multi-token form (decode_body.h) — the same plan, grid and workspace; the mask is their extra argument
-template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE = false> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const uint32_t* tree_mask = nullptr) {
-    if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
-    if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
-    const size_t smem = (size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2;
+// The post-launch check of every launch sequence below.
+static int launch_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VATTN_K_OK : fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
+}
+
+// What both decode launches (stream plan / grid heuristics) settle before their attention kernel: the dynamic LDS — merge area >= V staging
+// (DC_WAVES x 8 KiB) — and where the new K/V rows are written: by the attention kernel itself (fused_append: ONE new row, not the multi-token
+// form), else by a separate append launch in front of it on the same stream (seqlen_knew > 1; the multi-token form, which has no fused
+// rotation either).
+struct decode_launch { size_t smem; int fused_append; };
+template <int HD, bool MT> static decode_launch begin_decode_launch(const vattn_attn_params* p, hipStream_t st) {
     const int fused_append = (!MT && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
     if (p->k_new && !fused_append) launch_append(p, st);
+    return {(size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2, fused_append};
+}
+// The last kernel argument of every build: the mask words of the TREE builds, an empty struct for the others (decode_body.h, tree_mask_arg)
+template <bool TREE> static tree_mask_arg<TREE> mask_arg(const uint32_t* tree_mask) {
+    if constexpr (TREE) return tree_mask; else return {};
+}
+
+// WIN: the sliding-window builds (decode_body.h) — taken iff the block carries a window, so a window-less call runs the kernels it always ran
+// MT: the multi-token builds — no fused append, no fused rotation (ROPE 0)
+// TREE: the tree-masked builds of the multi-token form (decode_body.h) — the same plan, grid and workspace; the mask is their extra argument
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const uint32_t* tree_mask) {
+    if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
+    if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
+    const decode_launch l = begin_decode_launch<HD, MT>(p, st);
     const dim3 grid((unsigned)nwg, (unsigned)p->h_k), block(64 * DC_WAVES);
-    if constexpr (MT) {
-        // multi-token form: the append is the launch above (rows land before the attention launch on the same stream), no fused rotation
-        if constexpr (TREE) hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, false, true, true>), grid, block, smem, st, *p, 1, 0, tree_mask);
-        else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, WIN, true>), grid, block, smem, st, *p, 1, 0);
-        hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB, true>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
-        return VATTN_K_OK;
-    } else if constexpr (__is_same(T, __bf16)) {
+    auto kernel = decode_stream_kernel<T, HD, true, NB, MT ? 0 : -1, WIN, MT, TREE>;
+    if constexpr (!MT && __is_same(T, __bf16)) {
         // bf16 rotates through fp32 (no packed arithmetic): with the fused-RoPE path compiled in, decode_stream_kernel<bf16, 128, one head block> is
         // 12 registers over the 168 of three workgroups per CU and gets a scratch segment — 9 us per launch even when no rotation is asked for
         // (profiles/r06_decode_bf16_scratch.txt).  Two builds: without the path (what the reference's wrapper calls: no spill), and the one that
         // takes it at run time (the path compiled in UNCONDITIONALLY spills more: 46 registers instead of 12).
-        if (p->rotary_cos_sin) hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, -1, WIN>), grid, block, smem, st, *p, 1, fused_append);
-        else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, 0, WIN>), grid, block, smem, st, *p, 1, fused_append);
-    } else hipLaunchKernelGGL((decode_stream_kernel<T, HD, true, NB, -1, WIN>), grid, block, smem, st, *p, 1, fused_append);
-    hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
-    return VATTN_K_OK;
+        if (!p->rotary_cos_sin) kernel = decode_stream_kernel<T, HD, true, NB, 0, WIN, MT, TREE>;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, l.smem, st, *p, 1, l.fused_append, mask_arg<TREE>(tree_mask));
+    hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB, MT>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
+    return launch_status();
 }
 
-template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE = false> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask = nullptr) {
-    constexpr int W = DC_WAVES;
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
     if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT, TREE>(p, st, nwg, tree_mask);
     const int groups = decode_groups(p);
     const bool planned = p->split_items != nullptr;
     if (planned && (!p->split_seq || p->num_split_items <= 0)) return fail(VATTN_K_ERR_INVALID, "split_items needs split_seq and num_split_items");
     const int splits = planned ? 2 : pick_splits(p, groups, decode_slots(p));
     if (splits > 1 && !p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
-    dim3 grid(splits, p->h_k * groups, p->b), block(64 * W);
+    dim3 grid(splits, p->h_k * groups, p->b), block(64 * DC_WAVES);
     if (planned) grid = dim3((unsigned)p->num_split_items, p->h_k * groups, 1);
     if (groups > 1 && !(p->variant & 64) && !planned) {            // sibling groups share an XCD (variant bit 6: plain 3-D grid, for A/B)
         const long w = (long)splits * p->h_k * p->b;
         grid = dim3((unsigned)(((w + 7) / 8) * 8 * groups));
     }
-    const size_t smem = (size_t)W * 16 * HD * 4 + W * 16 * 4 * 2;   // merge area >= V staging (W x 8 KiB)
-    const int fused_append = (!MT && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
-    if (p->k_new && !fused_append) launch_append(p, st);        // seqlen_knew > 1, multi-token form: separate append launch
-    const vattn_attn_params& q = *p;
-    if constexpr (TREE) hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, false, true, true>), grid, block, smem, st, q, splits, groups, fused_append, tree_mask);
-    else hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT>), grid, block, smem, st, q, splits, groups, fused_append);
+    const decode_launch l = begin_decode_launch<HD, MT>(p, st);
+    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT, TREE>), grid, block, l.smem, st, *p, splits, groups, l.fused_append, mask_arg<TREE>(tree_mask));
     const int sq = MT ? p->seqlen_q : 1;
-    if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, q);
-    else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * sq * p->h), dim3(128), 0, st, q, splits, sq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
-    return VATTN_K_OK;
+    if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, *p);
+    else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * sq * p->h), dim3(128), 0, st, *p, splits, sq);
+    return launch_status();
 }
 
-template <typename T, int HD, bool MT> int launch_decode_w(const vattn_attn_params* p, hipStream_t st) {
-    if (p->window_left_plus1 > 0) return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, true, MT>(p, st) : launch_decode_nb<T, HD, 1, true, MT>(p, st);
-    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, false, MT>(p, st) : launch_decode_nb<T, HD, 1, false, MT>(p, st);
+// The builds a block takes, from the top: TREE (vattn_tree_attn_with_kvcache: the caller checked multitoken_form(p) and that the block carries
+// no window — the multi-token launch of the same block, planners, grids, append and merges, on the TREE builds), else one token or the
+// multi-token form (the caller checked multitoken_form(p)), with or without a window; then one or two head blocks per workgroup.
+template <typename T, int HD, bool WIN, bool MT, bool TREE> int launch_decode_w(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
+    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, WIN, MT, TREE>(p, st, tree_mask) : launch_decode_nb<T, HD, 1, WIN, MT, TREE>(p, st, tree_mask);
 }
-template <typename T, int HD> int launch_decode_t(const vattn_attn_params* p, hipStream_t st) {
-    if (p->seqlen_q == 1) return launch_decode_w<T, HD, false>(p, st);
-    return launch_decode_w<T, HD, true>(p, st);      // the multi-token form (the caller checked multitoken_form(p))
+template <typename T, int HD, bool TREE> int launch_decode_t(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
+    if constexpr (TREE) return launch_decode_w<T, HD, false, true, true>(p, st, tree_mask);
+    else {
+        const bool win = p->window_left_plus1 > 0;
+        if (p->seqlen_q == 1) return win ? launch_decode_w<T, HD, true, false, false>(p, st, nullptr) : launch_decode_w<T, HD, false, false, false>(p, st, nullptr);
+        return win ? launch_decode_w<T, HD, true, true, false>(p, st, nullptr) : launch_decode_w<T, HD, false, true, false>(p, st, nullptr);
+    }
 }
-
-int launch_decode_form(const vattn_attn_params* p, hipStream_t st) {
+// dtype x head dimension: the one ladder of both entry points
+template <bool TREE> static int launch_decode_dtype_hd(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
     const bool f16 = p->dtype == VATTN_DTYPE_F16;
-    if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64>(p, st) : launch_decode_t<__bf16, 64>(p, st);
-    return f16 ? launch_decode_t<_Float16, 128>(p, st) : launch_decode_t<__bf16, 128>(p, st);
+    if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64, TREE>(p, st, tree_mask) : launch_decode_t<__bf16, 64, TREE>(p, st, tree_mask);
+    return f16 ? launch_decode_t<_Float16, 128, TREE>(p, st, tree_mask) : launch_decode_t<__bf16, 128, TREE>(p, st, tree_mask);
 }
-
-// vattn_tree_attn_with_kvcache (the caller checked multitoken_form(p) and that the block carries no window): the multi-token launch of
-// the same block — planners, grids, append, merges — on the TREE builds
-template <typename T, int HD> static int launch_tree_t(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) {
-    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, false, true, true>(p, st, tree_mask) : launch_decode_nb<T, HD, 1, false, true, true>(p, st, tree_mask);
-}
-int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) {
-    const bool f16 = p->dtype == VATTN_DTYPE_F16;
-    if (p->d == 64) return f16 ? launch_tree_t<_Float16, 64>(p, tree_mask, st) : launch_tree_t<__bf16, 64>(p, tree_mask, st);
-    return f16 ? launch_tree_t<_Float16, 128>(p, tree_mask, st) : launch_tree_t<__bf16, 128>(p, tree_mask, st);
-}
+int launch_decode_form(const vattn_attn_params* p, hipStream_t st) { return launch_decode_dtype_hd<false>(p, st, nullptr); }
+int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) { return launch_decode_dtype_hd<true>(p, st, tree_mask); }
 
 // Length-balanced split of a ragged decode batch (include/vattn_kernels.h, vattn_decode_plan).  Every sequence is cut into pieces of at
 // most T tiles; T is the smallest piece length for which the pieces of ALL sequences fit the resident workgroups in one round

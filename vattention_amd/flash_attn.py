@@ -34,6 +34,12 @@ Deliberate difference: the reference raises "If key is supplied, 
 <= the seqlen of the KV cache" when the GQA-swapped seqlen_q exceeds the cache view (contexts shorter
 than Hq/Hkv tokens) and its wrapper then silently returns unwritten output; this shim raises that
 message only when the new keys genuinely do not fit, and otherwise always computes.
+
+Call path:  flash_attn_with_kvcache / flash_attn_tree_with_kvcache (varlen: its own layout, the same helpers)
+  -> _build_block: the shared checks, `out` / LSE, the tensor, stride and shape fields of an AttnParams
+  -> the entry's own fields (window, causal, variant, rotary, hints, plans | the Sq rule, the mask words) and _set_scalars
+  -> _launch / _launch_tree (relaunch: the fast path of a block already launched) -> _issue: workspace, call, rc -> exception
+  -> the C ABI (include/vattn_kernels.h: vattn_flash_attn_with_kvcache / vattn_tree_attn_with_kvcache).
 """
 from __future__ import annotations
 
@@ -75,10 +81,14 @@ def _rotary_table(rotary_cos, rotary_sin, _rotary_cos_sin, rotary_interleaved, q
     return t
 
 
+def _stream_key(device, stream_ptr=None):
+    return (device.index if device.index is not None else torch.cuda.current_device(),
+            stream_ptr if stream_ptr is not None else torch.cuda.current_stream(device).cuda_stream)
+
+
 def _workspace(nbytes: int, device, stream_ptr=None) -> torch.Tensor:
     # one scratch buffer per (device, stream): split-KV partials of calls on different streams must not share storage
-    key = (device.index if device.index is not None else torch.cuda.current_device(),
-           stream_ptr if stream_ptr is not None else torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device, stream_ptr)
     ws = _workspaces.get(key)
     if ws is None or ws.numel() * 4 < nbytes:
         ws = torch.empty((max(nbytes, 1 << 20) + 3) // 4, dtype=torch.float32, device=device)
@@ -139,7 +149,7 @@ def hybrid_attn(prefill_call, decode_call, device, _role_mode: int = 0, _product
     # library's entry point of the same name, which issues the two launches back to back
     lib = K.klib() if _product else K.klib_lab()
     need = lib.vattn_hybrid_workspace_bytes(C.byref(pp), C.byref(pd))
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device)
     ws = _hybrid_ws.get(key)
     if ws is None or ws.numel() * 4 < need:
         ws = torch.zeros((max(need, 1 << 20) + 3) // 4, dtype=torch.float32, device=device)      # zero ONCE: see the header
@@ -166,37 +176,134 @@ def relaunch(p, q_ptr: int, k_new_ptr: int, v_new_ptr: int, out_ptr: int, k_cach
         _launch(p, dev)
         return
     # (the block's library and workspace need were settled by its first launch: a batch-1 decode is tens of microseconds per layer, and
-    # every host microsecond on this path shows up as an idle GPU)
-    lib, need = fast
+    # every host microsecond on this path shows up as an idle GPU: no workspace-bytes call, no library lookup)
+    _issue(p, dev, *fast)
+
+
+def _issue(p, dev, lib, need=None, mask=None):
+    """The one launch: the workspace the call needs (asked of the library unless `need` is known: relaunch) from the per-(device, stream)
+    cache, the call on the current stream — the tree-masked entry point iff `mask` is given — and its return code as an exception (the
+    tree entry's -10 names the rule of its gate that the block breaks: NotImplementedError).  Returns the workspace need."""
+    if need is None:
+        need = (lib.vattn_attn_workspace_bytes if mask is None else lib.vattn_tree_attn_workspace_bytes)(C.byref(p))
     st = K.current_stream_ptr(dev)
     if need:
-        p.workspace = _workspace(need, dev, st).data_ptr()
-    rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
+        p.workspace = _workspace(need, dev, st).data_ptr()   # kept alive by the per-(device, stream) cache until a larger one replaces it
+    if mask is None:
+        rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
+    else:
+        rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
     if rc != 0:
-        raise RuntimeError(K.last_error(lib))
+        raise (NotImplementedError if mask is not None and rc == -10 else RuntimeError)(K.last_error(lib))
+    return need
 
 
 def _launch(p, dev, keep=()):
-    """Attach the split-KV workspace the call needs (one buffer per device and stream) and launch on the current stream."""
+    """Launch block `p` on the current stream (or record it: hybrid_attn)."""
     if _capture is not None:
         _capture.append((p, keep))
         return
     lib = K.klib_for(p.variant)          # the product library; the lab build only for measurement variants (tests, kbench)
-    need = lib.vattn_attn_workspace_bytes(C.byref(p))
-    st = K.current_stream_ptr(dev)
-    if need:
-        ws = _workspace(need, dev, st)   # kept alive by the per-(device, stream) cache until a larger one replaces it
-        p.workspace = ws.data_ptr()
-    rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
-    if rc != 0:
-        raise RuntimeError(K.last_error(lib))
-    p._fast = (lib, need)                # relaunch(): same shapes, same plan
+    p._fast = (lib, _issue(p, dev, lib))      # relaunch(): same shapes, same plan
+
+
+def _launch_tree(p, mask: torch.Tensor, dev, keep=()):
+    """_launch for the tree-masked entry point (vattn_tree_attn_with_kvcache): the product library only; a block outside the gate has a
+    workspace need of 0 and is refused by the call."""
+    _issue(p, dev, K.klib(), None, mask)
 
 
 def _check_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError("vattention_amd.flash_attn: tensors must live on the GPU (there is no CPU path)")
+
+
+def _check_dtypes(q, k_cache, v_cache):
+    if k_cache.dtype != q.dtype:
+        raise RuntimeError("query and key must have the same dtype")
+    if v_cache.dtype != q.dtype:
+        raise RuntimeError("query and value must have the same dtype")
+
+
+def _index_tensor(t, name):
+    if t.dtype != torch.int32:
+        raise RuntimeError(name + " must have dtype int32")
+    return t.contiguous()
+
+
+def _check_out(out, q):
+    """`out` mirrors the optional out_ of the reference's C++ entry point (flash_api.cpp:1303)."""
+    if out is None:
+        return torch.empty_like(q)
+    if out.dtype != q.dtype:
+        raise RuntimeError("Output must have the same dtype as inputs")
+    if out.shape != q.shape or out.stride(-1) != 1:
+        raise RuntimeError("Output tensor must have the shape of q and a contiguous last dimension")
+    return out
+
+
+def _set_q_out(p, q, out):
+    # (batch, row, head) strides; the flattened [T, Hq, D] tokens of the varlen entry have no batch dimension: stride 0
+    p.q, p.out = q.data_ptr(), out.data_ptr()
+    p.q_batch_stride, p.q_row_stride, p.q_head_stride = ((0,) + q.stride())[-4:-1]
+    p.o_batch_stride, p.o_row_stride, p.o_head_stride = ((0,) + out.stride())[-4:-1]
+
+
+def _set_scalars(p, q, num_splits, softmax_scale):
+    p.dtype = K.dtype_code(q.dtype)
+    p.num_splits = int(num_splits)
+    p.softmax_scale = float(q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale)
+
+
+def _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse):
+    """The shared front half of the [B, Sq, Hq, D]-query entry points: argument checks (wording as flash_api.cpp), `out` / LSE, and an
+    AttnParams with its tensor, stride and shape fields filled.  Returns (block, the tensors it points to — to be kept alive —,
+    out, lse, (B, Sq, Sk, Sn, D), device); in the tuple, cache_seqlens / cache_batch_idx are the normalised int32 tensors."""
+    _check_cuda(q, k_cache, v_cache, k, v)
+    assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
+    assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
+    mc = lambda x: x.contiguous() if x is not None and x.stride(-1) != 1 else x
+    q, k, v = mc(q), mc(k), mc(v)
+    B, Sq, Hq, D = q.shape
+    Bc, Sk, Hkv, Dk = k_cache.shape
+    _check_dtypes(q, k_cache, v_cache)
+    dev = q.device
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=dev)
+    if cache_seqlens is not None:
+        cache_seqlens = _index_tensor(cache_seqlens, "seqlens_k")
+        assert cache_seqlens.shape == (B,)
+    if cache_batch_idx is not None:
+        cache_batch_idx = _index_tensor(cache_batch_idx, "cache_batch_idx")
+    elif Bc < B:
+        raise RuntimeError("batch size of the cache is smaller than the batch size of q")
+    Sn = 0
+    if k is not None:
+        if v is None:
+            raise RuntimeError("If key is supplied, value must also be passed in")
+        if cache_seqlens is None:
+            raise RuntimeError("If key is supplied, seqlens_k must also be passed in")
+        Sn = k.shape[1]
+        if Sn > Sk:
+            raise RuntimeError(APPEND_ERR)
+        assert k.shape == (B, Sn, Hkv, D) and v.shape == (B, Sn, Hkv, D)
+    out = _check_out(out, q)
+    lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_softmax_lse else None
+
+    p = K.AttnParams()
+    _set_q_out(p, q, out)
+    _set_cache(p, k_cache, v_cache)
+    if k is not None:
+        p.k_new, p.v_new = k.data_ptr(), v.data_ptr()
+        p.knew_batch_stride, p.knew_row_stride, p.knew_head_stride = k.stride(0), k.stride(1), k.stride(2)
+        p.vnew_batch_stride, p.vnew_row_stride, p.vnew_head_stride = v.stride(0), v.stride(1), v.stride(2)
+    p.cache_seqlens = cache_seqlens.data_ptr() if cache_seqlens is not None else None
+    p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
+    p.softmax_lse = lse.data_ptr() if lse is not None else None
+    p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, Sq, Sk, Sn, Hq, Hkv, D
+    p.split_reserved = _STREAM_SWITCH
+    return p, (q, k, v, k_cache, v_cache, cache_seqlens, cache_batch_idx, out, lse), out, lse, (B, Sq, Sk, Sn, D), dev
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None,
@@ -211,76 +318,17 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         raise NotImplementedError("paged KV (block_table) is what vAttention replaces; not supported")
     if alibi_slopes is not None or cache_leftpad is not None or softcap != 0.0:
         raise NotImplementedError("alibi / leftpad / softcap are not used by the vAttention path")
-    _check_cuda(q, k_cache, v_cache, k, v)
-    assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
-    assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
-    mc = lambda x: x.contiguous() if x is not None and x.stride(-1) != 1 else x
-    q, k, v = mc(q), mc(k), mc(v)
-    B, Sq, Hq, D = q.shape
-    Bc, Sk, Hkv, Dk = k_cache.shape
-    if k_cache.dtype != q.dtype:
-        raise RuntimeError("query and key must have the same dtype")
-    if v_cache.dtype != q.dtype:
-        raise RuntimeError("query and value must have the same dtype")
-    if softmax_scale is None:
-        softmax_scale = D ** (-0.5)
-    dev = q.device
+    p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse)
     # host-side bound on the sequences' lengths (sizes the prefill KV split): known when cache_seqlens is an int or the
     # caller (the attention wrapper, which has the lengths on the host) passes _max_seqlen_k; else the cache's row count
     hint = int(_max_seqlen_k)
-    if cache_seqlens is not None and isinstance(cache_seqlens, int):
-        hint = hint or cache_seqlens + (k.shape[1] if k is not None else 0)
-        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=dev)
-    if cache_seqlens is not None:
-        if cache_seqlens.dtype != torch.int32:
-            raise RuntimeError("seqlens_k must have dtype int32")
-        cache_seqlens = cache_seqlens.contiguous()
-        assert cache_seqlens.shape == (B,)
-    if cache_batch_idx is not None:
-        if cache_batch_idx.dtype != torch.int32:
-            raise RuntimeError("cache_batch_idx must have dtype int32")
-        cache_batch_idx = cache_batch_idx.contiguous()
-    elif Bc < B:
-        raise RuntimeError("batch size of the cache is smaller than the batch size of q")
-    Sn = 0
-    if k is not None:
-        if v is None:
-            raise RuntimeError("If key is supplied, value must also be passed in")
-        if cache_seqlens is None:
-            raise RuntimeError("If key is supplied, seqlens_k must also be passed in")
-        Sn = k.shape[1]
-        if Sn > Sk:
-            raise RuntimeError(APPEND_ERR)
-        assert k.shape == (B, Sn, Hkv, D) and v.shape == (B, Sn, Hkv, D)
-    if out is None:        # `out` mirrors the optional out_ of the reference's C++ entry point (flash_api.cpp:1303)
-        out = torch.empty_like(q)
-    else:
-        if out.dtype != q.dtype:
-            raise RuntimeError("Output must have the same dtype as inputs")
-        if out.shape != q.shape or out.stride(-1) != 1:
-            raise RuntimeError("Output tensor must have the shape of q and a contiguous last dimension")
-    lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_softmax_lse else None
-
-    p = K.AttnParams()
-    p.q, p.out = q.data_ptr(), out.data_ptr()
-    p.q_batch_stride, p.q_row_stride, p.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
-    p.o_batch_stride, p.o_row_stride, p.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
-    _set_cache(p, k_cache, v_cache)
-    if k is not None:
-        p.k_new, p.v_new = k.data_ptr(), v.data_ptr()
-        p.knew_batch_stride, p.knew_row_stride, p.knew_head_stride = k.stride(0), k.stride(1), k.stride(2)
-        p.vnew_batch_stride, p.vnew_row_stride, p.vnew_head_stride = v.stride(0), v.stride(1), v.stride(2)
-    p.cache_seqlens = cache_seqlens.data_ptr() if cache_seqlens is not None else None
-    p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
-    p.softmax_lse = lse.data_ptr() if lse is not None else None
-    p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, Sq, Sk, Sn, Hq, Hkv, D
+    if isinstance(cache_seqlens, int):
+        hint = hint or cache_seqlens + Sn
+    k, cache_seqlens, cache_batch_idx = keep[1], keep[5], keep[6]
     p.window_left_plus1, causal = _window_left_plus1(window_size, bool(causal), Sq, Sk)
     p.is_causal = 1 if causal else 0
-    p.dtype = K.dtype_code(q.dtype)
-    p.num_splits = int(num_splits)
-    p.softmax_scale = float(softmax_scale)
+    _set_scalars(p, keep[0], num_splits, softmax_scale)
     p.variant = int(_variant)
-    p.split_reserved = _STREAM_SWITCH
     if rot is not None:
         p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
     # A few query rows per entry (the verify step of speculative decoding): the library runs them on the split-KV decode kernels (the
@@ -324,7 +372,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
             p.num_splits = -int(_plan_tiles)
         plan = _decode_plan(p, _cache_seqlens_host, dev)      # ragged batch: work items of near-equal length (None: uniform split)
         p.num_splits = 0
-    _launch(p, dev, keep=(q, k, v, k_cache, v_cache, cache_seqlens, cache_batch_idx, out, lse, rot, plan))
+    _launch(p, dev, keep=keep + (rot, plan))
     if _params_out is not None and not return_softmax_lse:
         # the caller may re-issue this call through relaunch(): the block keeps the index / length / rotary tensors it points to alive
         p._keep = (cache_seqlens, cache_batch_idx, rot, plan)
@@ -346,20 +394,6 @@ def _pack_tree_mask(tree_mask, B: int, Sq: int, dev) -> torch.Tensor:
     return tree_mask.contiguous()
 
 
-def _launch_tree(p, mask: torch.Tensor, dev, keep=()):
-    """_launch for the tree-masked entry point (vattn_tree_attn_with_kvcache): the product library only."""
-    lib = K.klib()
-    st = K.current_stream_ptr(dev)
-    need = lib.vattn_tree_attn_workspace_bytes(C.byref(p))      # (0 for a block outside the gate: the call below refuses it)
-    if need:
-        p.workspace = _workspace(need, dev, st).data_ptr()
-    rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
-    if rc == -10:
-        raise NotImplementedError(K.last_error(lib))
-    if rc != 0:
-        raise RuntimeError(K.last_error(lib))
-
-
 def flash_attn_tree_with_kvcache(q, k_cache, v_cache, tree_mask, k=None, v=None, cache_seqlens: Optional[Union[int, torch.Tensor]] = None,
                                  cache_batch_idx: Optional[torch.Tensor] = None, softmax_scale=None, return_softmax_lse=False, out=None,
                                  _num_splits: int = 0):
@@ -370,65 +404,12 @@ def flash_attn_tree_with_kvcache(q, k_cache, v_cache, tree_mask, k=None, v=None,
     [B, Sq, Sq] / [Sq, Sq] tensor ([.., t, s]; packed on the device, broadcast over the batch).  Any pattern is legal; a node that sees no
     key gives 0 (LSE +inf).  No causal flag (the mask is the rule), no window, no rotary: calls outside the gate raise NotImplementedError
     naming the rule.  `_num_splits` < 0: the decode kernels' forced grids (tests, A/B).  Works under graph capture like decode.  Afterwards `cache_ops.keep_rows` makes the accepted path contiguous."""
-    _check_cuda(q, k_cache, v_cache, k, v)
-    assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
-    assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
-    mc = lambda x: x.contiguous() if x is not None and x.stride(-1) != 1 else x
-    q, k, v = mc(q), mc(k), mc(v)
-    B, Sq, Hq, D = q.shape
-    Bc, Sk, Hkv, Dk = k_cache.shape
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise RuntimeError("query, key and value must have the same dtype")
-    dev = q.device
+    p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse)
     if not 2 <= Sq <= 8:
         raise NotImplementedError("a tree mask needs 2 <= seqlen_q <= 8 (one mask word of 8 bits per query token); got %d" % Sq)
     mask = _pack_tree_mask(tree_mask, B, Sq, dev)
-    if isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=dev)
-    if cache_seqlens is not None:
-        if cache_seqlens.dtype != torch.int32:
-            raise RuntimeError("seqlens_k must have dtype int32")
-        cache_seqlens = cache_seqlens.contiguous()
-        assert cache_seqlens.shape == (B,)
-    if cache_batch_idx is not None:
-        if cache_batch_idx.dtype != torch.int32:
-            raise RuntimeError("cache_batch_idx must have dtype int32")
-        cache_batch_idx = cache_batch_idx.contiguous()
-    elif Bc < B:
-        raise RuntimeError("batch size of the cache is smaller than the batch size of q")
-    Sn = 0
-    if k is not None:
-        if v is None:
-            raise RuntimeError("If key is supplied, value must also be passed in")
-        if cache_seqlens is None:
-            raise RuntimeError("If key is supplied, seqlens_k must also be passed in")
-        Sn = k.shape[1]
-        if Sn > Sk:
-            raise RuntimeError(APPEND_ERR)
-        assert k.shape == (B, Sn, Hkv, D) and v.shape == (B, Sn, Hkv, D)
-    if out is None:
-        out = torch.empty_like(q)
-    elif out.dtype != q.dtype or out.shape != q.shape or out.stride(-1) != 1:
-        raise RuntimeError("Output tensor must have the shape and dtype of q and a contiguous last dimension")
-    lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_softmax_lse else None
-    p = K.AttnParams()
-    p.q, p.out = q.data_ptr(), out.data_ptr()
-    p.q_batch_stride, p.q_row_stride, p.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
-    p.o_batch_stride, p.o_row_stride, p.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
-    _set_cache(p, k_cache, v_cache)
-    if k is not None:
-        p.k_new, p.v_new = k.data_ptr(), v.data_ptr()
-        p.knew_batch_stride, p.knew_row_stride, p.knew_head_stride = k.stride(0), k.stride(1), k.stride(2)
-        p.vnew_batch_stride, p.vnew_row_stride, p.vnew_head_stride = v.stride(0), v.stride(1), v.stride(2)
-    p.cache_seqlens = cache_seqlens.data_ptr() if cache_seqlens is not None else None
-    p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
-    p.softmax_lse = lse.data_ptr() if lse is not None else None
-    p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, Sq, Sk, Sn, Hq, Hkv, D
-    p.dtype = K.dtype_code(q.dtype)
-    p.num_splits = int(_num_splits)
-    p.softmax_scale = float(D ** (-0.5) if softmax_scale is None else softmax_scale)
-    p.split_reserved = _STREAM_SWITCH
-    _launch_tree(p, mask, dev, keep=(q, k, v, k_cache, v_cache, cache_seqlens, cache_batch_idx, out, lse, mask))
+    _set_scalars(p, keep[0], _num_splits, softmax_scale)      # (is_causal / variant stay 0: the mask is the rule, the product library the only one)
+    _launch_tree(p, mask, dev, keep=keep + (mask,))
     counters["tree_decode_calls"] += 1
     return (out, lse) if return_softmax_lse else out
 
@@ -633,43 +614,29 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q
         raise RuntimeError("q must be [total_tokens, num_heads, head_size]")
     T, Hq, D = q.shape
     Bc, Sk, Hkv, Dk = k_cache.shape
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise RuntimeError("query, key and value must have the same dtype")
-    for t, name in ((q_start, "q_start"), (q_lens, "q_lens"), (cache_seqlens, "seqlens_k")):
-        if t.dtype != torch.int32:
-            raise RuntimeError(name + " must have dtype int32")
+    _check_dtypes(q, k_cache, v_cache)
+    q_start, q_lens, cache_seqlens = _index_tensor(q_start, "q_start"), _index_tensor(q_lens, "q_lens"), _index_tensor(cache_seqlens, "seqlens_k")
     B = q_lens.shape[0]
     assert q_start.shape == (B,) and cache_seqlens.shape == (B,)
     if cache_batch_idx is not None:
-        if cache_batch_idx.dtype != torch.int32:
-            raise RuntimeError("cache_batch_idx must have dtype int32")
+        cache_batch_idx = _index_tensor(cache_batch_idx, "cache_batch_idx")
         assert cache_batch_idx.shape == (B,)
     elif Bc < B:
         raise RuntimeError("batch size of the cache is smaller than the number of chunks")
     if max_q_len < 2:
         raise RuntimeError("max_q_len must be >= 2 (single-token queries take the decode form)")
     assert k_cache.stride(-1) == 1 and v_cache.stride(-1) == 1 and q.stride(-1) == 1
-    if softmax_scale is None:
-        softmax_scale = D ** (-0.5)
-    if out is None:
-        out = torch.empty_like(q)
-    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
-        raise RuntimeError("Output tensor must have the shape and dtype of q and a contiguous last dimension")
+    out = _check_out(out, q)
     dev = q.device
     p = K.AttnParams()
-    p.q, p.out = q.data_ptr(), out.data_ptr()
-    p.q_batch_stride, p.q_row_stride, p.q_head_stride = 0, q.stride(0), q.stride(1)
-    p.o_batch_stride, p.o_row_stride, p.o_head_stride = 0, out.stride(0), out.stride(1)
+    _set_q_out(p, q, out)
     _set_cache(p, k_cache, v_cache)
-    p.cache_seqlens = cache_seqlens.contiguous().data_ptr()
-    p.cache_batch_idx = cache_batch_idx.contiguous().data_ptr() if cache_batch_idx is not None else None
-    p.q_start, p.q_lens = q_start.contiguous().data_ptr(), q_lens.contiguous().data_ptr()
+    p.cache_seqlens, p.q_start, p.q_lens = cache_seqlens.data_ptr(), q_start.data_ptr(), q_lens.data_ptr()
+    p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
     p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, int(max_q_len), Sk, 0, Hq, Hkv, D
     p.window_left_plus1, causal = _window_left_plus1(window_size, bool(causal), int(max_q_len), Sk)
     p.is_causal = 1 if causal else 0
-    p.dtype = K.dtype_code(q.dtype)
-    p.num_splits = int(num_splits)
-    p.softmax_scale = float(softmax_scale)
+    _set_scalars(p, q, num_splits, softmax_scale)
     p.variant = int(_variant)
     p.max_seqlen_k_hint = min(int(_max_seqlen_k), Sk) if _max_seqlen_k > 0 else 0
     if _rotary_cos_sin is not None:      # q rows of entry i are rotated at positions (cache_seqlens[i] - q_lens[i]) + row

@@ -140,23 +140,19 @@ def klib_for(variant: int):
     return klib_lab() if needs_lab(int(variant)) else klib()
 
 
-def describe(p, lib=None) -> dict:
-    """The launch plan of parameter block `p` (vattn_attn_plan_describe): pure host arithmetic."""
+def describe(p, lib=None, tree=False) -> dict:
+    """The launch plan of parameter block `p` (vattn_attn_plan_describe): pure host arithmetic.  tree: of its tree-masked call
+    (vattn_tree_attn_plan_describe) — the multi-token call's plan, or an error naming the rule of the gate the block breaks."""
+    lib = lib or klib()
     d = PlanDesc()
-    rc = (lib or klib()).vattn_attn_plan_describe(C.byref(p), C.byref(d))
+    rc = (lib.vattn_tree_attn_plan_describe if tree else lib.vattn_attn_plan_describe)(C.byref(p), C.byref(d))
     if rc != 0:
         raise RuntimeError(last_error(lib))
     return {n: int(getattr(d, n)) for n, _ in d._fields_}
 
 
 def describe_tree(p, lib=None) -> dict:
-    """The launch plan of the tree-masked call of block `p` (vattn_tree_attn_plan_describe): the multi-token call's, or an error naming
-    the rule of the gate the block breaks."""
-    d = PlanDesc()
-    rc = (lib or klib()).vattn_tree_attn_plan_describe(C.byref(p), C.byref(d))
-    if rc != 0:
-        raise RuntimeError(last_error(lib))
-    return {n: int(getattr(d, n)) for n, _ in d._fields_}
+    return describe(p, lib, tree=True)
 
 
 def last_error(lib=None) -> str:
