@@ -224,6 +224,12 @@ int fail(int code, const char* msg) {
     return code;
 }
 
+// The post-launch check of every launch sequence (decode_kernels.hip, prefill_kernels.hip).
+int launch_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VATTN_K_OK : fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
+}
+
 // the caller's header and ours describe the same block (include/vattn_kernels.h)
 bool abi_ok(const vattn_attn_params* p) { return p && p->struct_size == (uint32_t)sizeof(vattn_attn_params) && p->abi_version == VATTN_KERNELS_ABI; }
 

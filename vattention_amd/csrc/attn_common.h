@@ -269,7 +269,9 @@ __device__ __forceinline__ void prefill_release_and_merge(const vattn_attn_param
 
 // ---- host-side pieces shared by the translation units ----
 int fail(int code, const char* msg);                                    // attn_api.hip: records the message for vattn_kernels_last_error
+int launch_status();                                                    // attn_api.hip: hipGetLastError() as a return code (fail() on an error)
 void launch_append(const vattn_attn_params* p, hipStream_t st);         // cache_kernels.hip
+dim3 prefill_grid(const vattn_attn_params* p, int nqb, int nsplit, int* order_out);      // prefill_kernels.hip: grid and workgroup order of nqb query blocks in nsplit key-range shares
 int launch_prefill_form(const vattn_attn_params* p, hipStream_t st);    // prefill_kernels.hip (seqlen_q > 1)
 size_t prefill_workspace_bytes(const vattn_attn_params* p);
 int prefill_worklist(const vattn_attn_params* p, const int32_t* q_lens, const int32_t* k_lens, vattn_prefill_item* items, int cap_items,

@@ -204,12 +204,6 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
     return stream_table_bytes(p->b) + (size_t)(nwg + p->b) * p->h_k * rf * sizeof(float);      // (first record, count) per sequence, then the records
 }
 
-// The post-launch check of every launch sequence below.
-static int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VATTN_K_OK : fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
-}
-
 // What both decode launches (stream plan / grid heuristics) settle before their attention kernel: the dynamic LDS — merge area >= V staging
 // (DC_WAVES x 8 KiB) — and where the new K/V rows are written: by the attention kernel itself (fused_append: ONE new row, not the multi-token
 // form), else by a separate append launch in front of it on the same stream (seqlen_knew > 1; the multi-token form, which has no fused

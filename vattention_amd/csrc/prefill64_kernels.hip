@@ -59,23 +59,13 @@ namespace vattn_k {
 #undef P64_KERNEL_NAME
 #undef P64_WIN
 
-// host side: grid as prefill_kernels.hip's 1-D / 3-D orders with 256-row query blocks
-dim3 prefill_grid(const vattn_attn_params* p, int nqb, int* order_out);       // prefill_kernels.hip
-
+// host side: grid as prefill_kernels.hip's 1-D / 3-D orders (prefill_grid) with 256-row query blocks
 constexpr int kSmem64 = 36864 + 3 * PfSmem<128>::kTileBytes;      // K ring (2 x 17 408, rounded up) + V ring
 template <typename T, bool WIN> static void launch64_t(const vattn_attn_params* p, hipStream_t st, int nsplit) {
     const int nqb = (p->seqlen_q + 255) / 256;
     int order;
-    dim3 grid = prefill_grid(p, nqb, &order);
+    dim3 grid = prefill_grid(p, nqb, p->pf_items ? 1 : nsplit, &order);
     if (p->pf_items) grid = dim3((unsigned)p->num_pf_items);      // one workgroup per listed piece
-    else if (nsplit > 1) {
-        if (order == 0) {
-            vattn_attn_params q = *p;
-            q.variant = (p->variant & ~(3 << 5)) | (2 << 5);
-            grid = prefill_grid(&q, nqb, &order);
-        }
-        grid = dim3(((grid.x + 7) / 8) * 8 * nsplit);
-    }
     constexpr auto kern = WIN ? prefill64w_kernel<T> : prefill64_kernel<T>;
     static const bool once = [] {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem64 + 16);
@@ -88,10 +78,8 @@ template <typename T, bool WIN> static void launch64_t(const vattn_attn_params* 
 // ONE build per dtype, and one more for blocks that carry a sliding window (validate() keeps those off the work list); key-range shares are
 // merged by combine_rows_kernel / combine_blocks_kernel in a second launch (prefill_kernels.hip).
 void launch_prefill64(const vattn_attn_params* p, hipStream_t st, int nsplit) {
-    const bool win = p->window_left_plus1 > 0 && !p->pf_items;
-    if (p->dtype == VATTN_DTYPE_BF16) { if (win) launch64_t<__bf16, true>(p, st, nsplit); else launch64_t<__bf16, false>(p, st, nsplit); }
-    else if (win) launch64_t<_Float16, true>(p, st, nsplit);
-    else launch64_t<_Float16, false>(p, st, nsplit);
+    const bool win = p->window_left_plus1 > 0 && !p->pf_items, bf = p->dtype == VATTN_DTYPE_BF16;
+    (bf ? (win ? launch64_t<__bf16, true> : launch64_t<__bf16, false>) : (win ? launch64_t<_Float16, true> : launch64_t<_Float16, false>))(p, st, nsplit);
 }
 
 }  // namespace vattn_k

@@ -579,16 +579,11 @@ template <typename T, bool DYN> static void launch64p_t(const vattn_attn_params*
     hipLaunchKernelGGL((prefill64p_kernel<T, DYN, 24, 4>), dim3((unsigned)p->pf_num_wg), dim3(256), kSmem64p, st, *p, ctr);
 }
 
-// pf_wg_first given: the host-assigned queues; else the drawn ones (ctr: queue_counters(st), attn_api.hip)
+// pf_wg_first given: the host-assigned queues (no counters); else the drawn ones (ctr: queue_counters(st), attn_api.hip)
 void launch_prefill64p(const vattn_attn_params* p, hipStream_t st, int* ctr) {
     const bool bf = p->dtype == VATTN_DTYPE_BF16;
-    if (p->pf_wg_first) {
-        if (bf) launch64p_t<__bf16, false>(p, st, nullptr);
-        else launch64p_t<_Float16, false>(p, st, nullptr);
-    } else {
-        if (bf) launch64p_t<__bf16, true>(p, st, ctr);
-        else launch64p_t<_Float16, true>(p, st, ctr);
-    }
+    if (p->pf_wg_first) (bf ? launch64p_t<__bf16, false> : launch64p_t<_Float16, false>)(p, st, nullptr);
+    else (bf ? launch64p_t<__bf16, true> : launch64p_t<_Float16, true>)(p, st, ctr);
 }
 
 }  // namespace vattn_k

@@ -14,16 +14,8 @@
 
 #include "attn_common.h"
 
-namespace vattn_k {
-
-// ============================================================================================
-// prefill
-// ============================================================================================
-
-}  // namespace vattn_k
 #include "prefill_body.h"  // prefill_body / prefill_kernel
 namespace vattn_k {
-
 
 // Same merge for the KV-split prefill form, where there are b * sq * h output rows (tens of thousands) and at most 16
 // partials each: one WAVE per row (4 rows per 256-thread block), lane l < splits holds partial l's LSE, the weights are
@@ -114,12 +106,19 @@ __global__ __launch_bounds__(256) void combine_blocks_kernel(vattn_attn_params p
         p.softmax_lse[((int64_t)b * p.h + hh) * p.seqlen_q + q] = (wsum == 0.f) ? INFINITY : (mxs + __log2f(wsum)) * 0.6931471805599453f;
 }
 
+// "the kv heads divide the 8 XCDs": every XCD can then keep seeing ONE kv head (attn_common.h wg_to_work, order 2) — the rule of the grid
+// order below, and of the work lists' head order and queue classes
+static bool kv_heads_divide_xcds(const vattn_attn_params* p) { return p->h_k <= 8 && 8 % p->h_k == 0; }
+
 // variant bits 5-6: workgroup order (wg_to_work): 0 = default (XCD-grouped when the kv heads divide the 8 XCDs),
-// 1 = block-major per head (3-D grid), 2 = heaviest-first across heads, 3 = XCD-grouped
-dim3 prefill_grid(const vattn_attn_params* p, int nqb, int* order_out) {
+// 1 = block-major per head (3-D grid), 2 = heaviest-first across heads, 3 = XCD-grouped.
+// nsplit > 1 (key-range shares): the split lives in the 1-D orders, so the 3-D grid becomes heaviest-first across heads; the grid is
+// rounded up to runs of 8 ids (one per XCD), each repeated nsplit times.
+dim3 prefill_grid(const vattn_attn_params* p, int nqb, int nsplit, int* order_out) {
     int order = (p->variant >> 5) & 3;
     order = order == 0 ? 2 : order - 1;
-    if (order == 2 && !(p->h_k <= 8 && 8 % p->h_k == 0)) order = 1;
+    if (order == 2 && !kv_heads_divide_xcds(p)) order = 1;
+    if (order == 0 && nsplit > 1) order = 1;
     dim3 grid(nqb, p->h, p->b);
     if (order == 1) grid = dim3((unsigned)(nqb * p->h * p->b));
     if (order == 2) {
@@ -127,6 +126,7 @@ dim3 prefill_grid(const vattn_attn_params* p, int nqb, int* order_out) {
         const long items = (long)nqb * p->b * (p->h / p->h_k);   // per kv head
         grid = dim3((unsigned)(8 * ((items + per - 1) / per)));
     }
+    if (nsplit > 1) grid = dim3(((grid.x + 7) / 8) * 8 * nsplit);
     *order_out = order;
     return grid;
 }
@@ -142,10 +142,10 @@ PrefillPlan plan_prefill(const vattn_attn_params* p) {
     pl.tiling = (p->variant >> 1) & 7;
     pl.nsplit = 1;
     const bool auto_tiling = pl.tiling == 0;
-    // 2 (64-row waves) and 6 (hand-interleaved, software-pipelined) exist for d = 128 only; 3 and 5 were the compiler-scheduled
-    // pipelined and the phase-staggered kernels of round 1 (both slower, removed: profiles/r01_prefill_ablations.md)
-    if (pl.tiling == 3 || pl.tiling == 5 || (p->d != 128 && (pl.tiling == 2 || pl.tiling == 6 || pl.tiling == 7))) pl.tiling = 1;
-    if (pl.tiling == 2 || pl.tiling == 6) pl.tiling = 1;     // lab-only kernels (tools/lab/csrc/prefill_kernels_lab.hip; validate() rejects them before this)
+    // The product runs tilings 0/1, 4 and — d = 128 only — 7; every other selector describes as tiling 1 (validate() rejects it in front of
+    // a launch).  2 (64-row waves) and 6 (hand-interleaved, software-pipelined) are lab-only kernels (tools/lab/csrc/prefill_kernels_lab.hip);
+    // 3 and 5 were the compiler-scheduled pipelined and the phase-staggered kernels of round 1 (both slower, removed: profiles/r01_prefill_ablations.md)
+    if (!(pl.tiling <= 1 || pl.tiling == 4 || (pl.tiling == 7 && p->d == 128))) pl.tiling = 1;
     // keys an average query block sees.  Without a host-side bound the cache VIEW's row count stands in for the lengths, exactly as in
     // FlashAttention's own heuristic (flash_api.cpp:258-323 sizes the split from seqlen_k = k_cache.size(1)); the kernels divide the keys a
     // block REALLY sees (device-side lengths), so an over-estimate costs balance, never correctness.  [Rounds 1-3 assumed seqlen_q here:
@@ -244,22 +244,21 @@ PrefillPlan plan_prefill(const vattn_attn_params* p) {
     return pl;
 }
 
+// The merge launch behind a grid launch whose key ranges were split (kernel: combine_rows_kernel<T, HD>, named by the caller)
+static void launch_combine_rows(void (*kernel)(vattn_attn_params, int, int, int64_t), const vattn_attn_params* p, hipStream_t st, int nsplit) {
+    if (nsplit <= 1) return;
+    const int64_t rows = (int64_t)p->b * p->seqlen_q * p->h;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, *p, nsplit, p->seqlen_q, rows);
+}
+
 // (the single-launch merge of the key-range shares — variant bits 14 / 15 — measured slower and lives in the lab copy: profiles/r02_kbench_prefill_merge.txt)
 template <typename T, int HD, int WAVES, int QC, bool WIN = false> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit) {
     constexpr bool MSUM = false;
     constexpr int BM = 32 * QC * WAVES;
     const int nqb = (p->seqlen_q + BM - 1) / BM;
     int order;
-    dim3 grid = prefill_grid(p, nqb, &order);
+    const dim3 grid = prefill_grid(p, nqb, nsplit, &order);
     const dim3 block(64 * WAVES);
-    if (nsplit > 1) {
-        if (order == 0) {      // the split lives in the 1-D orders
-            vattn_attn_params q = *p;
-            q.variant = (p->variant & ~(3 << 5)) | (2 << 5);
-            grid = prefill_grid(&q, nqb, &order);
-        }
-        grid = dim3(((grid.x + 7) / 8) * 8 * nsplit);
-    }
     const size_t smem = PfSmem<HD>::kTotal;
     static const bool attr_once = [] {   // 64 KiB of dynamic LDS per workgroup
         (void)hipFuncSetAttribute((const void*)prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
@@ -267,10 +266,13 @@ template <typename T, int HD, int WAVES, int QC, bool WIN = false> void launch_p
     }();
     (void)attr_once;
     hipLaunchKernelGGL((prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>), grid, block, smem, st, *p, order, nqb, nsplit);
-    if (nsplit > 1) {
-        const int64_t rows = (int64_t)p->b * p->seqlen_q * p->h;
-        hipLaunchKernelGGL((combine_rows_kernel<T, HD>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, *p, nsplit, p->seqlen_q, rows);
-    }
+    launch_combine_rows(combine_rows_kernel<T, HD>, p, st, nsplit);
+}
+
+// A work list grouped by workgroup (vattn_prefill_plan_wg) runs on persistent workgroups (prefill64p_kernels.hip); the fused-RoPE form and
+// outputs without 16-byte rows keep one workgroup per piece (the queue order is a valid list order).  Asked by the launch AND by its description.
+static bool persistent_list(const vattn_attn_params* p) {
+    return p->pf_num_wg > 0 && !p->rotary_cos_sin && ((p->o_row_stride | p->o_head_stride | p->o_batch_stride) & 7) == 0;
 }
 
 template <typename T, int HD> int launch_prefill_t(const vattn_attn_params* p, hipStream_t st) {
@@ -279,10 +281,8 @@ template <typename T, int HD> int launch_prefill_t(const vattn_attn_params* p, h
         if (p->pf_items) {        // host-planned work list: prefill64 pieces longest first, then the merge of the split blocks
             if (p->num_pf_items <= 0 || (p->num_pf_blocks > 0 && (!p->pf_blocks || !p->workspace)))
                 return fail(VATTN_K_ERR_INVALID, "pf_items needs num_pf_items, and pf_blocks + a workspace when blocks are split");
-            // grouped by workgroup (vattn_prefill_plan_wg): persistent workgroups, continuous tile stream (prefill64p_kernels.hip);
-            // the fused-RoPE form and outputs without 16-byte rows keep one workgroup per piece (the queue order is a valid list order)
             int* ctr = nullptr;
-            bool persistent = p->pf_num_wg > 0 && !p->rotary_cos_sin && ((p->o_row_stride | p->o_head_stride | p->o_batch_stride) & 7) == 0;
+            bool persistent = persistent_list(p);
             if (persistent && !p->pf_wg_first) {      // drawn queues need the library's counters (none while a graph is being captured before they exist)
                 ctr = queue_counters(st);
                 // the counters are zeroed IN FRONT OF every drawn launch, stream-ordered (a memset node when captured): a graph replayed
@@ -293,33 +293,165 @@ template <typename T, int HD> int launch_prefill_t(const vattn_attn_params* p, h
             if (persistent) launch_prefill64p(p, st, ctr);
             else launch_prefill64(p, st, 1);
             if (p->num_pf_blocks > 0) hipLaunchKernelGGL((combine_blocks_kernel<T, 128>), dim3((unsigned)p->num_pf_blocks * 64), dim3(256), 0, st, *p);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
-            return VATTN_K_OK;
+            return launch_status();
         }
     }
     const PrefillPlan pl = plan_prefill(p);
     if (pl.nsplit > 1 && !p->workspace) return fail(VATTN_K_ERR_INVALID, "KV-split prefill needs a workspace (vattn_attn_workspace_bytes)");
-    bool launched = false;
     if constexpr (HD == 128) {
         if (pl.tiling == 7) {
             launch_prefill64(p, st, pl.nsplit);
-            if (pl.nsplit > 1) {
-                const int64_t rows = (int64_t)p->b * p->seqlen_q * p->h;
-                hipLaunchKernelGGL((combine_rows_kernel<T, 128>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, *p, pl.nsplit, p->seqlen_q, rows);
-            }
-            launched = true;
+            launch_combine_rows(combine_rows_kernel<T, 128>, p, st, pl.nsplit);
+            return launch_status();
         }
     }
     // (a block that carries a sliding window takes the WIN builds, a window-less one the kernels it always ran)
     const bool win = p->window_left_plus1 > 0;
-    if (launched) {
-    } else if (pl.tiling == 4) { if (win) launch_prefill<T, HD, 4, 1, true>(p, st, pl.nsplit); else launch_prefill<T, HD, 4, 1>(p, st, pl.nsplit); }
-    else if (win) launch_prefill<T, HD, 8, 1, true>(p, st, pl.nsplit);
-    else launch_prefill<T, HD, 8, 1>(p, st, pl.nsplit);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
-    return VATTN_K_OK;
+    if (pl.tiling == 4) (win ? launch_prefill<T, HD, 4, 1, true> : launch_prefill<T, HD, 4, 1>)(p, st, pl.nsplit);
+    else (win ? launch_prefill<T, HD, 8, 1, true> : launch_prefill<T, HD, 8, 1>)(p, st, pl.nsplit);
+    return launch_status();
+}
+
+// ---- the rules of the work-list planner (prefill_worklist below), each stated once ----
+namespace {
+// key tiles that query block qb of entry e walks
+static long tiles_of(const vattn_attn_params* p, const int32_t* q_lens, const int32_t* k_lens, int e, int qb) {
+    const long sq = q_lens ? q_lens[e] : p->seqlen_q, lk = k_lens[e];
+    long n_end = lk;
+    if (p->is_causal) { const long lim = (long)qb * 256 + 256 + (lk - sq); n_end = lim < lk ? lim : lk; }
+    if (n_end < 0) n_end = 0;
+    return (n_end + PF_BN - 1) / PF_BN;
+}
+static long query_blocks(const vattn_attn_params* p, const int32_t* q_lens, int e) { return ((q_lens ? (long)q_lens[e] : p->seqlen_q) + 255) / 256; }
+
+// A block of t tiles in pieces of at most T: ns EQUAL shares (not T, T, ..., remainder: the same count, no runt); share s is tiles [begin(s), end(s))
+struct Cut {
+    long t, ns, per;
+    Cut(long t_, long T) : t(t_), ns(std::max(1L, (t_ + T - 1) / T)), per((t_ + ns - 1) / ns) {}
+    long begin(long s) const { return std::min(t, s * per); }
+    long end(long s) const { return std::min(t, (s + 1) * per); }
+};
+
+// A piece's cost in half-tile units: its tiles, the per-piece overhead (6 = cold prologue: Q, the first DMA round trips, the first S'; 2 = chained
+// behind another piece of a persistent workgroup's queue), + 1.5 tiles for a piece that publishes a partial
+static long piece_cost(long tiles, long ovh, bool shared) { return 2 * tiles + ovh + (shared ? 3 : 0); }
+
+// The h pieces of one length are neighbours in the list and land on XCD (position % 8): enumerate the heads so that an XCD keeps seeing ONE
+// kv head (the grid orders' rule, attn_common.h wg_to_work), when the head counts allow it
+static int head_at(const vattn_attn_params* p, int j) {
+    if (p->h % 8 != 0 || !kv_heads_divide_xcds(p)) return j;
+    const int x = j % 8, r = j / 8, kv = x % p->h_k, G = p->h / p->h_k;
+    return kv * G + (x / p->h_k) * (p->h / 8) + r;
+}
+
+// The replay of the dispatcher (pieces longest first, each to the CU that frees up first), priced per candidate piece length T.  Every head
+// repeats a block's pieces, so the piece costs are kept as (cost, multiplicity) pairs — a few dozen for a one-prompt launch.  Costs and loads
+// are small integers (half-tile units) and the least loaded CU's load never decreases, so the CUs' loads are a COUNT PER LOAD VALUE with a
+// pointer at the smallest occupied one: k pieces of one cost move k CUs from load m to m + cost in one step.  The loads after every
+// assignment are the same multiset that sorting all pieces and a std::priority_queue of 256 loads produce (equal costs, equal loads are
+// interchangeable), for a twentieth of the host time: the plan is built once per engine iteration in front of layer 0's launch, with the GPU
+// idle (round 5: 0.9-2.7 ms -> 0.05-0.15 ms for one to three prompts on a TP8 rank, tools/plan_time.py).
+struct ReplayPrice {
+    const std::vector<long>& blk_tiles;                // per (entry, query block); every head repeats it
+    const long h, slots, ovh;
+    std::vector<std::pair<long, long>> cm;             // (cost in half-tile units, how many pieces have it)
+    std::vector<int> at_load;                          // CUs per load value
+    double operator()(long T, long* pieces_out, long* rows_out) {
+        cm.clear();
+        long rows = 0, pieces = 0, total = 0, maxc = 0;
+        for (long t : blk_tiles) {
+            const Cut cut(t, T);
+            if (cut.ns > 16) return 1e30;
+            for (long s_ = 0; s_ < cut.ns; s_++) {
+                const long c = piece_cost(cut.end(s_) - cut.begin(s_), ovh, cut.ns > 1);
+                cm.emplace_back(c, h);
+                total += c * h;
+                maxc = c > maxc ? c : maxc;
+            }
+            pieces += cut.ns * h;
+            if (cut.ns > 1) rows += 256 * cut.ns * h;
+        }
+        std::sort(cm.begin(), cm.end(), std::greater<std::pair<long, long>>());      // longest first
+        // (the least loaded CU is never above the final average, total / slots: no load exceeds that + the largest cost)
+        at_load.assign((size_t)(total / slots + maxc + 2), 0);
+        at_load[0] = (int)slots;
+        size_t mn = 0;
+        long makespan = 0;
+        for (const auto& cmi : cm) {
+            long left = cmi.second;
+            while (left > 0) {
+                while (at_load[mn] == 0) mn++;
+                const long k = left < at_load[mn] ? left : at_load[mn];
+                at_load[mn] -= (int)k;
+                at_load[mn + (size_t)cmi.first] += (int)k;
+                const long l = (long)mn + cmi.first;
+                makespan = l > makespan ? l : makespan;
+                left -= k;
+            }
+        }
+        *pieces_out = pieces;
+        *rows_out = rows;
+        // merge pass: every partial row is written once and read once (516 B each way) at ~3 TB/s, in half-tile units of ~0.9 us
+        return (double)makespan + (double)rows * 1032.0 / 3.0e12 / 0.9e-6;
+    }
+};
+
+}  // namespace
+
+// candidate piece lengths T, longest first: the longest block cut in {1 .. 16} equal shares, and FRACTIONS of the longest block in between — T =
+// 0.9 x longest cuts only the top tenth of the blocks (in two), which is what evens out the tail of a greedy longest-first schedule at the
+// price of few partials (modelled on the replay's tensor-parallel batches: 4-7 % on one-prompt launches, tools/)
+static std::vector<long> candidate_lengths(long longest, long min_piece) {
+    static const long kShares[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
+    static const double kFractions[] = {0.95, 0.9, 0.85, 0.8, 0.75, 0.7, 0.65, 0.6, 0.55, 0.45, 0.4, 0.36, 0.3};
+    std::vector<long> cands;
+    for (long ns_max : kShares) {
+        const long t_c = (longest + ns_max - 1) / ns_max;
+        if (t_c < min_piece && ns_max > 1) break;      // pieces shorter than ~12 tiles are all prologue
+        cands.push_back(t_c);
+    }
+    for (double f : kFractions) {
+        const long t_c = (long)(longest * f);
+        if (t_c >= min_piece && t_c * 16 >= longest) cands.push_back(t_c);
+    }
+    std::sort(cands.begin(), cands.end(), std::greater<long>());
+    cands.erase(std::unique(cands.begin(), cands.end()), cands.end());
+    return cands;
+}
+
+// workgroups of a persistent launch over n pieces: at most one per piece and per slot, whole runs of 8 (one per XCD) when there are that many
+static long queue_count(long n, long slots) {
+    const long nwg = n < slots ? n : slots;
+    return nwg >= 8 ? nwg - nwg % 8 : nwg;
+}
+
+// Assignment of the n listed pieces (longest first, tile ranges not yet open-ended) to nwg queues: workgroup w runs on XCD w % 8 (a grid of at most
+// one workgroup per CU is handed out round-robin), and an XCD's L2 should keep seeing ONE kv head: the pieces of kv head hk go to the
+// workgroups of class hk % ncls, ncls = the kv heads when they divide the 8 XCDs.  Longest first, each to the least loaded workgroup of
+// its class.  The items come back grouped by workgroup, queue w = [wg_first[w], wg_first[w + 1]).
+static void assign_queues(const vattn_attn_params* p, vattn_prefill_item* items, int n, long nwg, long ovh, int32_t* wg_first) {
+    const int G = p->h / p->h_k;
+    const int ncls = (nwg >= 8 && kv_heads_divide_xcds(p)) ? p->h_k : 1;
+    typedef std::pair<long, int> LW;                                        // (load in half-tile units, workgroup)
+    std::vector<std::priority_queue<LW, std::vector<LW>, std::greater<LW>>> heaps(ncls);
+    for (int w = 0; w < nwg; w++) heaps[(w % 8) % ncls].push(LW(4, w));     // every queue starts cold: + 4 over the chained overhead
+    std::vector<int> owner(n);
+    std::vector<int> fill(nwg + 1, 0);
+    for (int i = 0; i < n; i++) {
+        auto& hp = heaps[(items[i].h / G) % ncls];
+        LW top = hp.top();
+        hp.pop();
+        owner[i] = top.second;
+        fill[top.second + 1]++;
+        top.first += piece_cost((long)items[i].tile_end - items[i].tile_begin, ovh, items[i].nshares > 1);
+        hp.push(top);
+    }
+    for (int w = 0; w < nwg; w++) fill[w + 1] += fill[w];
+    std::vector<vattn_prefill_item> grouped(n);
+    std::vector<int> pos(fill.begin(), fill.end() - 1);
+    for (int i = 0; i < n; i++) grouped[pos[owner[i]]++] = items[i];        // stable: a queue keeps the longest-first order
+    for (int i = 0; i < n; i++) items[i] = grouped[i];
+    for (int w = 0; w <= nwg; w++) wg_first[w] = fill[w];
 }
 
 // Work list of a prefill launch (include/vattn_kernels.h, vattn_prefill_plan).  One 256-row prefill64 workgroup per CU; the launch
@@ -345,25 +477,21 @@ int prefill_worklist(const vattn_attn_params* p, const int32_t* q_lens, const in
     const long kSlots = persist && max_wg > 0 && max_wg < 256 ? max_wg : 256;      // one prefill64 workgroup per CU
     const long kOvh = persist ? 2 : 6;                 // per-piece overhead in half-tile units (chained / cold prologue)
     const long kMinPiece = persist ? 8 : 12;           // pieces shorter than this are all overhead
-    long W = 0, longest = 0, nblk = 0;
-    auto tiles_of = [&](int e, int qb) -> long {
-        const long sq = q_lens ? q_lens[e] : p->seqlen_q, lk = k_lens[e];
-        long n_end = lk;
-        if (p->is_causal) { const long lim = (long)qb * 256 + 256 + (lk - sq); n_end = lim < lk ? lim : lk; }
-        if (n_end < 0) n_end = 0;
-        return (n_end + PF_BN - 1) / PF_BN;
-    };
+    long W = 0, longest = 0, nblk = 0, nq_lo = 1L << 40, nq_hi = 0;
     std::vector<long> blk_tiles;                       // per (entry, query block); every head repeats it
     for (int e = 0; e < p->b; e++) {
-        const long sq = q_lens ? q_lens[e] : p->seqlen_q;
-        for (int qb = 0; qb < (sq + 255) / 256; qb++) {
-            const long t = tiles_of(e, qb);
+        const long nq = query_blocks(p, q_lens, e);
+        nq_lo = nq < nq_lo ? nq : nq_lo;
+        nq_hi = nq > nq_hi ? nq : nq_hi;
+        for (int qb = 0; qb < nq; qb++) {
+            const long t = tiles_of(p, q_lens, k_lens, e, qb);
             blk_tiles.push_back(t);
             W += t * p->h;
             nblk += p->h;
             longest = t > longest ? t : longest;
         }
     }
+    // ---- is a list wanted, and is its piece length searched? ----
     const long forced_T = p->num_splits < 0 ? -(long)p->num_splits : 0;      // num_splits = -T: pieces of at most T tiles, no questions asked
     // RAGGED batch of chunks: the default grid is (longest entry's blocks) x heads x entries, and the workgroups of the shorter entries
     // beyond their last block exit at once.  Harmless in number — but the hardware stripes consecutive workgroups of an XCD over its
@@ -371,146 +499,60 @@ int prefill_worklist(const vattn_attn_params* p, const int32_t* q_lens, const in
     // one launch take 1.60 ms against 1.14 + 0.12 ms launched one by one, while a third (1 000-token) entry — period 3 — brings the
     // launch to 1.18 ms (tools/tp8_prefill_probe.py, profiles/r03_tp8_prefill_probe.txt).  A ragged batch therefore ALWAYS gets a
     // list (valid blocks only, longest first), cut or not.
-    bool ragged = false;
-    if (q_lens && p->b > 1) {
-        long lo = 1L << 40, hi = 0;
-        for (int e = 0; e < p->b; e++) {
-            const long nq = ((long)q_lens[e] + 255) / 256;
-            lo = nq < lo ? nq : lo;
-            hi = nq > hi ? nq : hi;
-        }
-        ragged = lo != hi;
-    }
-    if (W <= 0 || nblk <= 0 || (!forced_T && !ragged && !persist && longest < 48)) return 0;
+    const bool ragged = q_lens && p->b > 1 && nq_lo != nq_hi;
+    const bool uncut_list = ragged || persist;         // a list is worth having even when no block is cut: compacted / chained on persistent workgroups
+    // several rounds of blocks are balanced by the dispatcher's longest-first order already, and short key walks (no block of 48 tiles) are
+    // prologue and merge: nothing to cut there
+    const bool search = !forced_T && nblk < 4 * kSlots && longest >= 48;
+    if (W <= 0 || nblk <= 0 || !(forced_T || uncut_list || search)) return 0;      // the default launch
     if (persist && nblk > cap_items) return 0;
     const long avg = (W + kSlots - 1) / kSlots;
     // grids of several rounds of workgroups whose longest is no longer than ~a round's share are balanced by the dispatcher's
     // longest-first order already (and, when not ragged, keep the XCD-grouped grid order)
-    const bool balanced = nblk >= 4 * kSlots || (nblk >= kSlots && longest * 4 <= avg * 5);
     // (round 5: a "balanced" launch of fewer than four rounds is still priced below — greedy longest-first leaves a one-prompt launch on a
     // tensor-parallel shard 10-20 % above its average load, and cutting only its LONGEST blocks in two brings that back)
-    if (!forced_T && !ragged && balanced && !persist && nblk >= 4 * kSlots) return 0;
-    // The replay of the dispatcher, priced per candidate.  Every head repeats a block's pieces, so the piece costs are kept as (cost,
-    // multiplicity) pairs — a few dozen for a one-prompt launch.  Costs and loads are small integers (half-tile units) and the least
-    // loaded CU's load never decreases, so the CUs' loads are a COUNT PER LOAD VALUE with a pointer at the smallest occupied one: k
-    // pieces of one cost move k CUs from load m to m + cost in one step.  The loads after every assignment are the same multiset that
-    // sorting all pieces and a std::priority_queue of 256 loads produce (equal costs, equal loads are interchangeable), for a
-    // twentieth of the host time: the plan is built once per engine iteration in front of layer 0's launch, with the GPU idle (round 5:
-    // 0.9-2.7 ms -> 0.05-0.15 ms for one to three prompts on a TP8 rank, tools/plan_time.py).
-    std::vector<std::pair<long, long>> cm;             // (cost in half-tile units, how many pieces have it)
-    std::vector<int> at_load;                          // CUs per load value
-    auto price = [&](long T, long* pieces_out, long* rows_out) -> double {
-        cm.clear();
-        long rows = 0, pieces = 0, total = 0, maxc = 0;
-        for (long t : blk_tiles) {
-            long ns = (t + T - 1) / T;
-            if (ns < 1) ns = 1;
-            if (ns > 16) return 1e30;
-            const long per = (t + ns - 1) / ns;
-            for (long s_ = 0; s_ < ns; s_++) {
-                long tb = s_ * per, te = tb + per;
-                if (tb > t) tb = t;
-                if (te > t) te = t;
-                const long c = 2 * (te - tb) + kOvh + (ns > 1 ? 3 : 0);
-                cm.emplace_back(c, (long)p->h);
-                total += c * p->h;
-                maxc = c > maxc ? c : maxc;
-            }
-            pieces += ns * p->h;
-            if (ns > 1) rows += 256 * ns * p->h;
-        }
-        std::sort(cm.begin(), cm.end(), std::greater<std::pair<long, long>>());      // longest first
-        // (the least loaded CU is never above the final average, total / kSlots: no load exceeds that + the largest cost)
-        at_load.assign((size_t)(total / kSlots + maxc + 2), 0);
-        at_load[0] = (int)kSlots;
-        size_t mn = 0;
-        long makespan = 0;
-        for (const auto& cmi : cm) {
-            long left = cmi.second;
-            while (left > 0) {
-                while (at_load[mn] == 0) mn++;
-                const long k = left < at_load[mn] ? left : at_load[mn];
-                at_load[mn] -= (int)k;
-                at_load[mn + (size_t)cmi.first] += (int)k;
-                const long l = (long)mn + cmi.first;
-                makespan = l > makespan ? l : makespan;
-                left -= k;
-            }
-        }
-        *pieces_out = pieces;
-        *rows_out = rows;
-        // merge pass: every partial row is written once and read once (516 B each way) at ~3 TB/s, in half-tile units of ~0.9 us
-        return (double)makespan + (double)rows * 1032.0 / 3.0e12 / 0.9e-6;
-    };
-    // candidate piece lengths T: the longest block cut in {1 .. 16} equal shares, and FRACTIONS of the longest block in between — T = 0.9 x
-    // longest cuts only the top tenth of the blocks (in two), which is what evens out the tail of a greedy longest-first schedule at the
-    // price of few partials (modelled on the replay's tensor-parallel batches: 4-7 % on one-prompt launches, tools/)
-    static const long kShares[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
-    static const double kFractions[] = {0.95, 0.9, 0.85, 0.8, 0.75, 0.7, 0.65, 0.6, 0.55, 0.45, 0.4, 0.36, 0.3};
-    std::vector<long> cands;
-    for (long ns_max : kShares) {
-        const long t_c = (longest + ns_max - 1) / ns_max;
-        if (t_c < kMinPiece && ns_max > 1) break;      // pieces shorter than ~12 tiles are all prologue
-        cands.push_back(t_c);
-    }
-    for (double f : kFractions) {
-        const long t_c = (long)(longest * f);
-        if (t_c >= kMinPiece && t_c * 16 >= longest) cands.push_back(t_c);
-    }
-    std::sort(cands.begin(), cands.end(), std::greater<long>());
-    cands.erase(std::unique(cands.begin(), cands.end()), cands.end());
-    double best = 1e30, uncut = 1e30;
-    long T = 0, best_rows = 0;
+    const bool balanced = nblk >= 4 * kSlots || (nblk >= kSlots && longest * 4 <= avg * 5);
+    // ---- the piece length T: forced, searched (the cheapest candidate wins), or the longest block (nothing cut) ----
+    ReplayPrice price{blk_tiles, p->h, kSlots, kOvh, {}, {}};
+    long T = longest, best_rows = 0;
     if (forced_T) {
         long pieces = 0;
         T = forced_T;
         if (longest > 16 * T) T = (longest + 15) / 16;
         if (price(T, &pieces, &best_rows) >= 1e30 || pieces > cap_items) return 0;
+    } else if (search) {
+        double best = 1e30, uncut = 1e30;
+        T = 0;
+        for (long t_c : candidate_lengths(longest, kMinPiece)) {
+            long pieces = 0, rows = 0;
+            const double c = price(t_c, &pieces, &rows);
+            if (t_c == longest) uncut = c;
+            if (pieces > cap_items) continue;
+            if (c < best - 1e-9) { best = c; T = t_c; best_rows = rows; }
+        }
+        // a launch the dispatcher balances on its own keeps its blocks whole unless cutting buys at least 2 %
+        if (balanced && T < longest && best > 0.98 * uncut) { T = longest; best_rows = 0; }
     }
-    const bool search = !forced_T && nblk < 4 * kSlots && longest >= 48;      // several rounds of blocks / short key walks: nothing to cut
-    if (!forced_T && !search) T = longest;
-    for (long t_c : cands) {
-        if (!search) break;
-        long pieces = 0, rows = 0;
-        const double c = price(t_c, &pieces, &rows);
-        if (t_c == longest) uncut = c;
-        if (pieces > cap_items) continue;
-        if (c < best - 1e-9) { best = c; T = t_c; best_rows = rows; }
-    }
-    // a launch the dispatcher balances on its own keeps its blocks whole unless cutting buys at least 2 %
-    if (search && balanced && T < longest && best > 0.98 * uncut) { T = longest; best_rows = 0; }
-    if (T == 0 || (!forced_T && !ragged && !persist && T >= longest)) return 0;      // nothing worth cutting, nothing to compact: the default launch
+    if (T == 0 || (!forced_T && !uncut_list && T >= longest)) return 0;      // nothing fits / nothing worth cutting, nothing to compact: the default launch
     if (best_rows > 0x7fffffffL - 4096) return 0;
+    // ---- emission: every (entry, query block, head), its shares ----
     int n = 0, nb = 0;
     long part_rows = 0;
     size_t bi = 0;
+    std::vector<int> heads(p->h);
+    for (int j = 0; j < p->h; j++) heads[j] = head_at(p, j);
     for (int e = 0; e < p->b; e++) {
-        const long sq = q_lens ? q_lens[e] : p->seqlen_q;
-        for (int qb = 0; qb < (sq + 255) / 256; qb++) {
-            const long t = blk_tiles[bi++];
-            long ns = (t + T - 1) / T;
-            if (ns < 1) ns = 1;
-            const long per = (t + ns - 1) / ns;
-            for (int j = 0; j < p->h; j++) {
-                // the h pieces of one length are neighbours in the list and land on XCD (position % 8): enumerate the heads so that an
-                // XCD keeps seeing ONE kv head (the grid orders' rule, attn_common.h wg_to_work), when the head counts allow it
-                int h = j;
-                if (p->h % 8 == 0 && p->h_k <= 8 && 8 % p->h_k == 0) {
-                    const int x = j % 8, r = j / 8, kv = x % p->h_k, G = p->h / p->h_k;
-                    h = kv * G + (x / p->h_k) * (p->h / 8) + r;
-                }
+        for (int qb = 0, nq = (int)query_blocks(p, q_lens, e); qb < nq; qb++) {
+            const Cut cut(blk_tiles[bi++], T);
+            const int32_t ns = (int32_t)cut.ns;
+            for (const int h : heads) {
                 if (ns > 1) {
                     if (nb >= cap_blocks) return 0;
-                    blocks[nb] = vattn_prefill_item{e, h, qb, 0, 0, (int32_t)ns, (int32_t)part_rows, 0};
-                    nb++;
+                    blocks[nb++] = vattn_prefill_item{e, h, qb, 0, 0, ns, (int32_t)part_rows, 0};
                 }
                 for (long s_ = 0; s_ < ns; s_++) {
                     if (n >= cap_items) return 0;
-                    long tb = s_ * per, te = tb + per;
-                    if (tb > t) tb = t;
-                    if (te > t) te = t;
-                    items[n] = vattn_prefill_item{e, h, qb, (int32_t)tb, (int32_t)te, (int32_t)ns, ns > 1 ? (int32_t)(part_rows + 256 * s_) : -1, s_ == ns - 1 ? 1 : 0};
-                    n++;
+                    items[n++] = vattn_prefill_item{e, h, qb, (int32_t)cut.begin(s_), (int32_t)cut.end(s_), ns, ns > 1 ? (int32_t)(part_rows + 256 * s_) : -1, s_ == ns - 1 ? 1 : 0};
                 }
                 if (ns > 1) part_rows += 256 * ns;
             }
@@ -520,54 +562,19 @@ int prefill_worklist(const vattn_attn_params* p, const int32_t* q_lens, const in
     std::stable_sort(items, items + n, [](const vattn_prefill_item& a, const vattn_prefill_item& c) {
         return (a.tile_end - a.tile_begin) > (c.tile_end - c.tile_begin);
     });
+    // persistent workgroups: host-assigned queues, or drawn ones — the list then stays in longest-first order (its head enumeration already
+    // deals the kv heads to the XCDs by position); the workgroups take piece w first and draw the rest (csrc/prefill64p_kernels.hip)
+    const long nwg = queue_count(n, kSlots);
+    if (persist_mode == 1) assign_queues(p, items, n, nwg, kOvh, wg_first);
     // The list is a PERFORMANCE hint, never a statement about the data: the last share of every query block is open-ended (the kernel
     // clamps every range to the tiles the block really sees, computed from the device-side lengths), so a caller whose host-side lengths
     // are stale gets the right result at a worse balance instead of dropped keys.
-    std::vector<long> piece_tiles(n);
-    for (int i = 0; i < n; i++) {
-        piece_tiles[i] = (long)items[i].tile_end - items[i].tile_begin;
+    for (int i = 0; i < n; i++)
         if (items[i].reserved) items[i].tile_end = 0x7fffffff;
-    }
     counts[0] = n;
     counts[1] = nb;
     counts[2] = (int32_t)part_rows;
-    if (persist_mode == 2) {
-        // drawn queues: the list stays in longest-first order (its head enumeration already deals the kv heads to the XCDs by position);
-        // the workgroups take piece w first and draw the rest (csrc/prefill64p_kernels.hip)
-        long nwg = n < kSlots ? n : kSlots;
-        if (nwg >= 8) nwg -= nwg % 8;
-        counts[3] = (int32_t)nwg;
-    } else if (persist) {
-        // ---- assignment: at most kSlots workgroups; workgroup w runs on XCD w % 8 (a grid of at most one workgroup per CU is handed out
-        // round-robin), and an XCD's L2 should keep seeing ONE kv head: the pieces of kv head hk go to the workgroups of class
-        // hk % ncls, ncls = the kv heads when they divide the 8 XCDs.  Longest first, each to the least loaded workgroup of its class. ----
-        long nwg = n < kSlots ? n : kSlots;
-        if (nwg >= 8) nwg -= nwg % 8;
-        const int G = p->h / p->h_k;
-        const int ncls = (nwg >= 8 && p->h_k <= 8 && 8 % p->h_k == 0) ? p->h_k : 1;
-        typedef std::pair<long, int> LW;                                        // (load in half-tile units, workgroup)
-        std::vector<std::priority_queue<LW, std::vector<LW>, std::greater<LW>>> heaps(ncls);
-        for (int w = 0; w < nwg; w++) heaps[(w % 8) % ncls].push(LW(4, w));     // every queue starts cold: + 4 over the chained overhead
-        std::vector<int> owner(n);
-        std::vector<int> fill(nwg + 1, 0);
-        for (int i = 0; i < n; i++) {
-            const long tiles = piece_tiles[i];
-            auto& hp = heaps[(items[i].h / G) % ncls];
-            LW top = hp.top();
-            hp.pop();
-            owner[i] = top.second;
-            fill[top.second + 1]++;
-            top.first += 2 * tiles + kOvh + (items[i].nshares > 1 ? 3 : 0);
-            hp.push(top);
-        }
-        for (int w = 0; w < nwg; w++) fill[w + 1] += fill[w];
-        std::vector<vattn_prefill_item> grouped(n);
-        std::vector<int> pos(fill.begin(), fill.end() - 1);
-        for (int i = 0; i < n; i++) grouped[pos[owner[i]]++] = items[i];        // stable: a queue keeps the longest-first order
-        for (int i = 0; i < n; i++) items[i] = grouped[i];
-        for (int w = 0; w <= nwg; w++) wg_first[w] = fill[w];
-        counts[3] = (int32_t)nwg;
-    }
+    if (persist) counts[3] = (int32_t)nwg;
     return n;
 }
 
@@ -582,7 +589,7 @@ void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (p->pf_items && p->d == 128) {
         out->path = 1;
         out->tiling = 7;
-        out->workgroups = p->pf_num_wg > 0 && !p->rotary_cos_sin && ((p->o_row_stride | p->o_head_stride | p->o_batch_stride) & 7) == 0 ? p->pf_num_wg : p->num_pf_items;
+        out->workgroups = persistent_list(p) ? p->pf_num_wg : p->num_pf_items;
         out->merge_launch = p->num_pf_blocks > 0;
         return;
     }
