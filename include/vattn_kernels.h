@@ -260,6 +260,44 @@ int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, 
                           const int32_t* keep_cnt,        /* device int32[b], 0..n_draft */
                           int32_t b, int32_t n_draft, int32_t h_k, int32_t d, int32_t dtype, void* stream);
 
+/* FP8 KV CACHE (OCP e4m3): halves the K/V bytes a decode step reads, doubles the tokens per physical page.  Additive: vattn_attn_params and
+ * VATTN_KERNELS_ABI are unchanged, the scale pointers travel BESIDE the parameter block as extra arguments of builds of the decode kernels
+ * of their own; every other kernel and entry point is what it was.
+ * STORAGE: OCP float8_e4m3fn, one byte per element, caches of the usual shape [batch_cache, rows, h_k, d]; last dimension contiguous, the
+ * other strides multiples of 16 elements (16-byte chunks).  SCALES: k_scale, v_scale are DEVICE float32[h_k], positive and finite; the host
+ * never dereferences them (calls stay graph-capturable).  value = stored * scale.
+ * QUANTISER (one answer for every input): (1) inv = 1.0f / scale by IEEE fp32 division, once per head; (2) y = float(x) * inv in fp32;
+ * (3) y is clamped to +-448 explicitly (v_med3), no conversion mode is relied on; (4) fp32 -> e4m3 with round-to-nearest-even; (5) a NaN
+ * input stores the NaN byte (0x7f, with the input's sign bit).  Bit-for-bit
+ * (x.float() * (1.0 / scale)).clamp(-448, 448).to(torch.float8_e4m3fn) on the CPU.
+ * READING: the decode kernels widen the bytes to the I/O dtype in registers — exact, e4m3 has 3 mantissa bits and |x| <= 448 — and run the
+ * f16 / bf16 MFMAs; q and P are not quantised.  The scales never touch an element: k_scale[hk] folds into the workgroup's softmax scale,
+ * v_scale[hk] into the final 1 / l normalisation (fp32, wave-uniform), so against the 2-byte kernels run on the dequantised values no
+ * rounding step is added. */
+
+/* cache_flat into an fp8 cache: k_cache[t*k_cache_stride + i] = quantise(key[t*key_stride + i], k_scale[i / head_size]), same for value,
+ * t < num_tokens, i < num_heads*head_size; nothing else is written (vattn_cache_flat's contract).  key / value are src_dtype
+ * (VATTN_DTYPE_F16 / _BF16), source strides in source elements, cache strides in bytes.  Whole 16-byte chunks are stored where head_size,
+ * the strides and the pointers allow (head_size % 16 == 0, source strides % 8 == 0, cache strides % 16 == 0, 16-byte aligned pointers). */
+int vattn_cache_flat_fp8(const void* key, const void* value, void* k_cache, void* v_cache, int64_t num_tokens, int32_t num_heads,
+                         int32_t head_size, int64_t key_stride, int64_t value_stride, int64_t k_cache_stride, int64_t v_cache_stride,
+                         int32_t src_dtype, const float* k_scale, const float* v_scale, void* stream);
+
+/* Decode over an fp8 cache.  p->dtype is the dtype of q / out / k_new / v_new (f16 or bf16); k_cache / v_cache point at fp8 bytes and their
+ * strides are in elements = bytes.  k_new / v_new (any count) are quantised into rows cache_seqlens[b] .. by an append launch in front of
+ * the attention launch on the same stream (no fused in-kernel append, no fused rotary in these builds).
+ * GATE: the one-token decode form (seqlen_q == 1) and the causal / non-causal multi-token form (its gate above).  Refused with
+ * VATTN_K_ERR_UNSUPPORTED and a message that names the rule: window_left_plus1 > 0, rotary_cos_sin, split_items, q_lens / pf_items, the
+ * prefill form, a -DVATTN_LAB build.  A tree mask and vattn_hybrid_attn have no fp8 entry point: their caches are 2-byte.  NULL scales:
+ * VATTN_K_ERR_INVALID.
+ * PLAN: planners, grids, stream decomposition, record layouts, merge / combine kernels and workspace sizes are those of
+ * vattn_flash_attn_with_kvcache for the same block — nothing is tuned apart; partials are fp32, published already scaled by v_scale, and do
+ * not know the cache dtype.  vattn_fp8kv_attn_workspace_bytes / _plan_describe answer what that call gets (0 / an error outside the gate).
+ * CONTRACT: as everywhere — no K/V load at or beyond Lk = cache_seqlens[b] + seqlen_knew. */
+int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream);
+size_t vattn_fp8kv_attn_workspace_bytes(const vattn_attn_params* p);
+int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
+
 /* Fused prefill || decode for a hybrid batch (replaces the reference's POD-Attention entry point
  * /root/reference/pod_attn/pod_attn/flash_attn_interface.py true_fused_attn_with_kvcache, call site
  * /root/reference/sarathi-lean/sarathi/model_executor/attention/vattention_flashattention_pod_wrapper.py:121-203): ONE launch of

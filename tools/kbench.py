@@ -3,7 +3,9 @@
 (vattn_time_attn) on the shapes of BASELINE.md §3 and prints TFLOP/s / GB/s against the rooflines.
 usage: python tools/kbench.py [prefill] [decode] [--variant N]
        python tools/kbench.py multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base LIB] [--bf16] [--tree]   (the multi-token decode form;
-                                                                          --tree: the tree-masked entry with a chain mask beside the causal call)"""
+                                                                          --tree: the tree-masked entry with a chain mask beside the causal call)
+       python tools/kbench.py decode --kv-fp8 [--only NAMES] / multitoken --kv-fp8 --mt ...   (the same call over an fp8 (e4m3) cache —
+                                                                          vattn_fp8kv_attn_with_kvcache — beside the 2-byte call, alternating, over rotating caches)"""
 import ctypes as C
 import os
 import sys
@@ -168,6 +170,64 @@ def decode(variant):
         del keep, kc, vc
 
 
+def fp8_ab(name, B, sq, Hq, Hkv, ctx, slots, ragged=False):
+    """--kv-fp8: the call (q [B, sq, Hq, 128], sq new rows appended at ctx - sq) over a 2-byte cache and over an fp8 (e4m3) cache of the same
+    values (quantised with per-head amax scales by vattn_cache_flat_fp8), ALTERNATING in one process, each over R caches in turn with
+    R x bytes >= 1.5 GB of the 2-byte caches (nothing is served from the 256 MiB Infinity Cache; the same R for both), warmed up, five
+    windows each; HIP events around each window.  Bytes = the K/V rows read + q and out, per cache dtype."""
+    from vattention_amd.cache_ops import cache_flat_fp8
+    torch.manual_seed(0)
+    lib, st = K.klib(), torch.cuda.current_stream().cuda_stream
+    by16 = B * 2.0 * ctx * Hkv * 128 * 2
+    R = max(2, int(1.5e9 // by16) + 1)
+    lens = [ctx - sq - (i * 7919 % (ctx - ctx // 8)) for i in range(B)] if ragged else [ctx - sq] * B
+    cl = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    idx = torch.arange(B, dtype=torch.int32, device=DEV) % slots
+    q = torch.randn(B, sq, Hq, 128, device=DEV, dtype=DTYPE)
+    kn, vn = torch.randn(B, sq, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, sq, Hkv, 128, device=DEV, dtype=DTYPE)
+    ks = torch.full((Hkv,), 6.0 / 448.0, dtype=torch.float32, device=DEV)       # N(0,1) data: amax over 10^8 samples is below 6
+    vs = ks.clone()
+    p16, p8 = [], []
+    for _ in range(R):
+        kc, vc = torch.randn(slots, ctx, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(slots, ctx, Hkv, 128, device=DEV, dtype=DTYPE)
+        k8, v8 = torch.empty(slots, ctx, Hkv, 128, device=DEV, dtype=torch.float8_e4m3fn), torch.empty(slots, ctx, Hkv, 128, device=DEV, dtype=torch.float8_e4m3fn)
+        cache_flat_fp8(kc.view(-1, Hkv, 128), vc.view(-1, Hkv, 128), k8.view(-1, Hkv, 128), v8.view(-1, Hkv, 128), ks, vs)
+        p16.append(params(q, kc, vc, cl, idx, kn, vn))
+        p8.append(params(q, k8, v8, cl, idx, kn, vn))          # (the workspace need is the 2-byte call's: the same planners)
+    d = K.describe_fp8kv(p8[0][0])
+    assert d == K.describe(p16[0][0])
+    call16 = lambda pp: lib.vattn_flash_attn_with_kvcache(C.byref(pp), st)
+    call8 = lambda pp: lib.vattn_fp8kv_attn_with_kvcache(C.byref(pp), ks.data_ptr(), vs.data_ptr(), st)
+    iters = max(2, 60 // R + 1)
+
+    def window(call, ps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            for pp, _k in ps:
+                if call(pp) != 0:
+                    raise RuntimeError(K.last_error(lib))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / (iters * len(ps)) * 1e3
+    for call, ps in ((call16, p16), (call8, p8)):              # warm-up: every cache of both
+        window(call, ps)
+    t16, t8 = [], []
+    for _rep in range(5):                                       # alternating windows
+        t16.append(window(call16, p16))
+        t8.append(window(call8, p8))
+    vis = sum(n + sq for n in lens)
+    b16 = vis * 2.0 * Hkv * 128 * 2 + 2.0 * B * sq * Hq * 128 * 2
+    b8 = vis * 2.0 * Hkv * 128 * 1 + 2.0 * B * sq * Hq * 128 * 2
+    m16, m8 = sorted(t16)[2], sorted(t8)[2]
+    print("  %-22s B=%3d sq=%d ctx=%6d Hq=%2d Hkv=%d  path %d tiling %d wg %d, %d rotating caches" % (name, B, sq, ctx, Hq, Hkv, d["path"], d["tiling"], d["workgroups"], R))
+    print("    2-byte cache : median %8.1f us  (5 windows: %s)  %7.1f GB/s = %.1f%% of 8000, %.1f%% of the 6290 GB/s read stream" % (
+        m16, " ".join("%.1f" % x for x in t16), b16 / m16 / 1e3, b16 / m16 / 1e3 / 80, b16 / m16 / 1e3 / 62.9))
+    print("    fp8 cache    : median %8.1f us  (5 windows: %s)  %7.1f GB/s = %.1f%% of 8000, %.1f%% of the 6290 GB/s read stream" % (
+        m8, " ".join("%.1f" % x for x in t8), b8 / m8 / 1e3, b8 / m8 / 1e3 / 80, b8 / m8 / 1e3 / 62.9))
+    print("    ratio 2-byte / fp8 : %.2fx" % (m16 / m8), flush=True)
+
+
 def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
     """The multi-token decode call (q [B, sq, Hq, 128] against `ctx` cached tokens, the sq new rows appended) on caches that ROTATE (as
     --rotate: the Infinity Cache serves no repeat): this tree, the one-token decode step of the same batch, the prefill form of the same
@@ -293,7 +353,11 @@ if __name__ == "__main__":
             sys.exit("kbench multitoken: give at least one --mt B,sq,Hq,Hkv,ctx[,ragged]")
         torch.zeros(1, device=DEV)
         for dims, ragged in shapes:
-            multitoken(*dims, ragged=ragged, base_path=base)
+            if "--kv-fp8" in sys.argv:
+                B_, sq_, Hq_, Hkv_, ctx_ = dims
+                fp8_ab("multi-token", B_, sq_, Hq_, Hkv_, ctx_ + sq_, B_, ragged)
+            else:
+                multitoken(*dims, ragged=ragged, base_path=base)
         sys.exit(0)
     what = [a for a in sys.argv[1:] if a in ("prefill", "decode")] or ["prefill", "decode"]
     torch.zeros(1, device=DEV)
@@ -301,7 +365,14 @@ if __name__ == "__main__":
         for v in VARIANTS:
             print("-- prefill variant %d (order %s, tiling %s) --" % (v, ["XCD-grouped (default)", "block-major per head", "heaviest-first across heads", "XCD-grouped"][(v >> 5) & 3] + (", prefill64 build %d" % ((v >> 8) & 15) if (v >> 8) & 15 else ""), {0: "default plan", 1: "8 waves x 32 rows", 2: "4 waves x 64 rows", 3: "8 waves x 32 rows, LDS-DMA ring, in-wave software pipeline (prefill32)", 4: "4 waves x 32 rows", 6: "8 waves, hand-interleaved MFMA/VALU groups", 7: "4 waves x 64 rows, LDS-DMA ring, in-wave software pipeline (prefill64)"}[(v >> 1) & 7]))
             prefill(v)
-    if "decode" in what:
+    if "decode" in what and "--kv-fp8" in sys.argv:
+        print("== decode (Sq=1, append + split-KV + combine) over a 2-byte and an fp8 (e4m3) cache, %s, D=128 ==" % ("bf16" if DTYPE == torch.bfloat16 else "fp16"))
+        for name, Hq, Hkv, B, ctx in [("llama8b B16@32k", 32, 8, 16, 32768), ("llama8b B1@128k", 32, 8, 1, 131072), ("yi6b B16@32k", 32, 4, 16, 32768),
+                                      ("llama8b B64@8k", 32, 8, 64, 8192), ("llama70b/tp8 B64@32k", 8, 1, 64, 32768), ("mqa G32 B16@16k", 32, 1, 16, 16384)]:
+            if ONLY and not any(o.strip() in name for o in ONLY.split(",")):
+                continue
+            fp8_ab(name, B, 1, Hq, Hkv, ctx, B)
+    elif "decode" in what:
         dvs = [variant]
         if "--dvariants" in sys.argv:
             dvs = [int(x) for x in sys.argv[sys.argv.index("--dvariants") + 1].split(",")]

@@ -29,6 +29,35 @@ def cache_flat(key: torch.Tensor, value: torch.Tensor, k_cache: torch.Tensor, v_
         raise RuntimeError(K.last_error())
 
 
+def cache_flat_fp8(key: torch.Tensor, value: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                   k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+    """MI355X extension (include/vattn_kernels.h, "FP8 KV cache"): cache_flat into a float8_e4m3fn cache — n new tokens of K and V
+    ([n, kvh, D], fp16 / bf16) are quantised with one scale per kv head (k_scale / v_scale: float32 [kvh] GPU tensors, value = stored *
+    scale) into caller-sliced cache rows, in place, on the current stream.  The bytes are those of
+    (x.float() * (1.0 / scale)).clamp(-448, 448).to(torch.float8_e4m3fn); nothing but rows [0, n) is written."""
+    ts = (key, value, k_cache, v_cache, k_scale, v_scale)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("vattention_amd.cache_ops: tensors must live on the GPU (there is no CPU path)")
+    if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+        raise RuntimeError("cache_flat_fp8 writes float8_e4m3fn caches")
+    if value.dtype != key.dtype:
+        raise RuntimeError("key and value must have the same dtype")
+    n, nh, hs = key.shape[0], key.shape[1], key.shape[2]
+    for s in (k_scale, v_scale):
+        if s.dtype != torch.float32 or s.shape != (nh,) or not s.is_contiguous():
+            raise RuntimeError("k_scale / v_scale must be contiguous float32 [num_kv_heads] tensors")
+    if n == 0:
+        return
+    for t in (key, value, k_cache, v_cache):
+        if t.stride(-1) != 1 or t.stride(-2) != hs:
+            raise RuntimeError("cache_flat_fp8 expects [tokens, heads, head_size] with contiguous (heads, head_size)")
+    rc = K.klib().vattn_cache_flat_fp8(key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), n, nh, hs,
+                                       key.stride(0), value.stride(0), k_cache.stride(0), v_cache.stride(0), K.dtype_code(key.dtype),
+                                       k_scale.data_ptr(), v_scale.data_ptr(), K.current_stream_ptr(key.device))
+    if rc != 0:
+        raise (NotImplementedError if rc == -10 else RuntimeError)(K.last_error())
+
+
 def cache_flat_rope(key: torch.Tensor, value: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                     cos_sin_cache: torch.Tensor, pos0: int) -> None:
     """MI355X extension: cache_flat with the rotary embedding of the KEY rows fused in — k_cache[t] = rope(key[t]) at

@@ -306,6 +306,18 @@ static const char* tree_gate_reason(const vattn_attn_params* p) {
 }
 static const char* kTreeWindow = "a tree mask cannot be combined with a sliding window (window_left_plus1 > 0): a node's position is its depth, not its index";
 
+
+// Why a block is outside the gate of the call over an fp8 (e4m3) cache (include/vattn_kernels.h) — rule by rule — or NULL when it passes
+static const char* fp8kv_gate_reason(const vattn_attn_params* p) {
+    if (kLab) return "the measurement build has no fp8 KV cache kernels (use libvattn_amd.so)";
+    if (p->window_left_plus1 > 0) return "an fp8 KV cache cannot be combined with a sliding window (window_left_plus1 > 0)";
+    if (p->rotary_cos_sin) return "an fp8 KV cache cannot be combined with fused rotary embedding (rotary_cos_sin): rotate q and k first";
+    if (p->split_items) return "an fp8 KV cache cannot be combined with split_items (host item plan)";
+    if (p->q_lens || p->pf_items) return "an fp8 KV cache cannot be combined with q_lens / pf_items (batched chunks, prefill work lists)";
+    if (!decode_form(p)) return "an fp8 KV cache is read by the decode kernels only: seqlen_q == 1 or the multi-token form, not the prefill form";
+    return nullptr;
+}
+
 }  // namespace vattn_k
 
 using namespace vattn_k;
@@ -353,6 +365,38 @@ int vattn_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* o
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);
     if (const char* why = tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    return vattn_attn_plan_describe(p, out);
+}
+
+int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream) {
+    if (!abi_ok(p)) return validate(p);
+    if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the fp8 rule)
+    int rc = validate(p);
+    if (rc) return rc;
+    if (!k_scale || !v_scale) return fail(VATTN_K_ERR_INVALID, "an fp8 KV cache needs k_scale and v_scale (device float32[h_k])");
+    const int64_t strides[] = {p->k_batch_stride, p->k_row_stride, p->k_head_stride, p->v_batch_stride, p->v_row_stride, p->v_head_stride};
+    for (int64_t s : strides)
+        if (s % 16 != 0) return fail(VATTN_K_ERR_UNSUPPORTED, "fp8 cache strides must be multiples of 16 elements (16-byte vector access)");
+    if (p->k_new && (((p->knew_batch_stride | p->knew_row_stride | p->knew_head_stride | p->vnew_batch_stride | p->vnew_row_stride | p->vnew_head_stride) & 7) ||
+                     ((((uintptr_t)p->k_new) | ((uintptr_t)p->v_new)) & 15)))
+        return fail(VATTN_K_ERR_UNSUPPORTED, "k_new / v_new must be 16-byte aligned (strides of 8 elements)");
+    if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
+#ifndef VATTN_LAB
+    return launch_fp8kv_form(p, k_scale, v_scale, (hipStream_t)stream);
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
+}
+
+// The call over an fp8 cache runs the launch of the same block on other builds of the same kernels: same planners, same answers.
+size_t vattn_fp8kv_attn_workspace_bytes(const vattn_attn_params* p) {
+    if (!abi_ok(p) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || fp8kv_gate_reason(p)) return 0;
+    return vattn_attn_workspace_bytes(p);
+}
+
+int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
+    if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
+    if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
     return vattn_attn_plan_describe(p, out);
 }
 

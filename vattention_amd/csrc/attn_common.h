@@ -271,6 +271,7 @@ __device__ __forceinline__ void prefill_release_and_merge(const vattn_attn_param
 int fail(int code, const char* msg);                                    // attn_api.hip: records the message for vattn_kernels_last_error
 int launch_status();                                                    // attn_api.hip: hipGetLastError() as a return code (fail() on an error)
 void launch_append(const vattn_attn_params* p, hipStream_t st);         // cache_kernels.hip
+void launch_append_fp8(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st);   // cache_kernels.hip: k_new / v_new quantised into an e4m3 cache
 dim3 prefill_grid(const vattn_attn_params* p, int nqb, int nsplit, int* order_out);      // prefill_kernels.hip: grid and workgroup order of nqb query blocks in nsplit key-range shares
 int launch_prefill_form(const vattn_attn_params* p, hipStream_t st);    // prefill_kernels.hip (seqlen_q > 1)
 size_t prefill_workspace_bytes(const vattn_attn_params* p);
@@ -285,6 +286,7 @@ void launch_prefill64(const vattn_attn_params* p, hipStream_t st, int nsplit, in
 int* merge_counters(hipStream_t st, size_t n_ints);                      // attn_api.hip: zeroed per-(device, stream) counters, NULL while capturing
 int launch_decode_form(const vattn_attn_params* p, hipStream_t st);     // decode_kernels.hip (decode_form(p): seqlen_q == 1, or the multi-token form)
 int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st);   // decode_kernels.hip (product library only): the tree-masked multi-token form
+int launch_fp8kv_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st);   // decode_kernels.hip (product library only): decode_form(p) over an e4m3 cache
 size_t decode_workspace_bytes(const vattn_attn_params* p);
 int decode_plan(const vattn_attn_params* p, const int32_t* lens, vattn_decode_item* items, int cap, int32_t* seq);   // decode_kernels.hip
 void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out);   // prefill_kernels.hip

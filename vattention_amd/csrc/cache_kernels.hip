@@ -179,6 +179,95 @@ __global__ void cache_keep_rows_kernel(uint16_t* k_cache, uint16_t* v_cache, int
         if (ok[j]) *(uint4*)(base + (int64_t)j * row_stride) = rows[j];
 }
 
+// ---- e4m3 KV cache: the quantiser (include/vattn_kernels.h, "FP8 KV cache") ----
+// One byte of the cache: y = float(x) * inv (inv = 1.0f / scale, IEEE division, once per head), clamped to +-448 by an explicit v_med3, converted
+// with round-to-nearest-even; a NaN stores the NaN byte (0x7f, with the input's sign: v_med3 would return a bound for it).
+__device__ __forceinline__ float fp8_clamp(float y) { return __builtin_amdgcn_fmed3f(y, -448.f, 448.f); }
+// 16 source elements (two 16-byte chunks) -> one 16-byte chunk of the cache
+template <typename T> __device__ __forceinline__ uint4 fp8_quant16(const T* src, const float inv) {
+    using V8 = typename Tr<T>::v8;
+    const V8 a = as_v8<V8>(*(const uint4*)src), b = as_v8<V8>(*(const uint4*)(src + 8));
+    float y[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        y[j] = (float)a[j] * inv;
+        y[8 + j] = (float)b[j] * inv;
+    }
+    unsigned w[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int r = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(y[4 * i]), fp8_clamp(y[4 * i + 1]), 0, false);
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(y[4 * i + 2]), fp8_clamp(y[4 * i + 3]), r, true);
+        unsigned u = (unsigned)r;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const float v = y[4 * i + e];
+            if (v != v) u = (u & ~(0xffu << (8 * e))) | ((0x7fu | ((__builtin_bit_cast(unsigned, v) >> 24) & 0x80u)) << (8 * e));
+        }
+        w[i] = u;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+template <typename T> __device__ __forceinline__ uint8_t fp8_quant1(const T x, const float inv) {
+    const float y = (float)x * inv;
+    if (y != y) return (uint8_t)(0x7fu | ((__builtin_bit_cast(unsigned, y) >> 24) & 0x80u));
+    return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(y), 0.f, 0, false) & 0xff);
+}
+
+// vattn_cache_flat_fp8: rows t < num_tokens of key / value [t * stride + head * hs + i] (T) -> cache bytes, one thread per 16 elements of
+// a row (VEC: two 16-byte loads, ONE 16-byte store per tensor) or per element (rows that are not 16-byte aligned).  Nothing else is written.
+template <typename T, bool VEC>
+__global__ void cache_flat_fp8_kernel(const T* __restrict__ key, const T* __restrict__ value, uint8_t* __restrict__ k_cache, uint8_t* __restrict__ v_cache,
+                                      int64_t num_tokens, int n, int hs, int64_t key_stride, int64_t value_stride, int64_t k_cache_stride,
+                                      int64_t v_cache_stride, const float* __restrict__ k_scale, const float* __restrict__ v_scale) {
+    constexpr int E = VEC ? 16 : 1;
+    const int per_row = n / E;
+    const int64_t total = num_tokens * per_row;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = i / per_row;
+        const int c = (int)(i - t * per_row) * E;
+        const int h = c / hs;
+        const float ik = 1.0f / k_scale[h], iv = 1.0f / v_scale[h];
+        if constexpr (VEC) {
+            *(uint4*)(k_cache + t * k_cache_stride + c) = fp8_quant16<T>(key + t * key_stride + c, ik);
+            *(uint4*)(v_cache + t * v_cache_stride + c) = fp8_quant16<T>(value + t * value_stride + c, iv);
+        } else {
+            k_cache[t * k_cache_stride + c] = fp8_quant1<T>(key[t * key_stride + c], ik);
+            v_cache[t * v_cache_stride + c] = fp8_quant1<T>(value[t * value_stride + c], iv);
+        }
+    }
+}
+
+// append_kv_kernel for an e4m3 cache: k_new / v_new [b, sn, h_k, d] (T) quantised into rows cache_seqlens[b] .. of slot cache_batch_idx[b];
+// cache strides are in bytes.  One thread per 16 elements; d is a multiple of 16 and every stride of the cache a multiple of 16 bytes.
+template <typename T>
+__global__ void append_kv_fp8_kernel(vattn_attn_params p, const float* __restrict__ k_scale, const float* __restrict__ v_scale) {
+    const int b = blockIdx.y;
+    const int slot = p.cache_batch_idx ? p.cache_batch_idx[b] : b;
+    const int len = p.cache_seqlens ? p.cache_seqlens[b] : p.seqlen_k;
+    const int cpr = p.d / 16;
+    const int total = p.seqlen_knew * p.h_k * cpr;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int c = i % cpr;
+        const int hk = (i / cpr) % p.h_k;
+        const int t = i / (cpr * p.h_k);
+        const int row = len + t;
+        if (row < 0 || row >= p.seqlen_k) continue;           // never write outside the cache view
+        const T* ksrc = (const T*)p.k_new + b * p.knew_batch_stride + t * p.knew_row_stride + hk * p.knew_head_stride + c * 16;
+        const T* vsrc = (const T*)p.v_new + b * p.vnew_batch_stride + t * p.vnew_row_stride + hk * p.vnew_head_stride + c * 16;
+        *(uint4*)((uint8_t*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)row * p.k_row_stride + hk * p.k_head_stride + c * 16) = fp8_quant16<T>(ksrc, 1.0f / k_scale[hk]);
+        *(uint4*)((uint8_t*)p.v_cache + (int64_t)slot * p.v_batch_stride + (int64_t)row * p.v_row_stride + hk * p.v_head_stride + c * 16) = fp8_quant16<T>(vsrc, 1.0f / v_scale[hk]);
+    }
+}
+
+void launch_append_fp8(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st) {
+    const int total = p->seqlen_knew * p->h_k * (p->d / 16);
+    if (total <= 0) return;
+    dim3 grid((total + 255) / 256, p->b), block(256);
+    if (p->dtype == VATTN_DTYPE_F16) hipLaunchKernelGGL(append_kv_fp8_kernel<_Float16>, grid, block, 0, st, *p, k_scale, v_scale);
+    else hipLaunchKernelGGL(append_kv_fp8_kernel<__bf16>, grid, block, 0, st, *p, k_scale, v_scale);
+}
+
 void launch_append(const vattn_attn_params* p, hipStream_t st) {
     const int total = p->seqlen_knew * p->h_k * (p->d / 8);
     dim3 grid((total + 255) / 256, p->b), block(256);
@@ -226,6 +315,33 @@ int vattn_cache_flat(const void* key, const void* value, void* k_cache, void* v_
         else
             return fail(VATTN_K_ERR_UNSUPPORTED, "cache_flat supports 2- and 4-byte element types");
     }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
+    return VATTN_K_OK;
+}
+
+int vattn_cache_flat_fp8(const void* key, const void* value, void* k_cache, void* v_cache, int64_t num_tokens, int32_t num_heads,
+                         int32_t head_size, int64_t key_stride, int64_t value_stride, int64_t k_cache_stride, int64_t v_cache_stride,
+                         int32_t src_dtype, const float* k_scale, const float* v_scale, void* stream) {
+    if (num_tokens <= 0) return VATTN_K_OK;
+    if (!key || !value || !k_cache || !v_cache) return fail(VATTN_K_ERR_INVALID, "null tensor pointer");
+    if (!k_scale || !v_scale) return fail(VATTN_K_ERR_INVALID, "cache_flat_fp8 needs k_scale and v_scale (device float32[num_heads])");
+    if (src_dtype != VATTN_DTYPE_F16 && src_dtype != VATTN_DTYPE_BF16) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_flat_fp8 quantises fp16 and bf16 sources");
+    if (num_heads <= 0 || head_size <= 0) return fail(VATTN_K_ERR_INVALID, "cache_flat_fp8: num_heads and head_size must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)num_heads * head_size;
+    const bool vec = head_size % 16 == 0 && ((key_stride | value_stride) & 7) == 0 && ((k_cache_stride | v_cache_stride) & 15) == 0 &&
+                     ((((uintptr_t)key) | ((uintptr_t)value) | ((uintptr_t)k_cache) | ((uintptr_t)v_cache)) & 15) == 0;
+    const int64_t total = num_tokens * (vec ? n / 16 : n);
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+#define VATTN_FLAT8(TT, VV)                                                                                                                 \
+    hipLaunchKernelGGL((cache_flat_fp8_kernel<TT, VV>), dim3((unsigned)blocks), dim3(256), 0, st, (const TT*)key, (const TT*)value,         \
+                       (uint8_t*)k_cache, (uint8_t*)v_cache, num_tokens, (int)n, (int)head_size, key_stride, value_stride, k_cache_stride,  \
+                       v_cache_stride, k_scale, v_scale)
+    if (src_dtype == VATTN_DTYPE_F16) { if (vec) VATTN_FLAT8(_Float16, true); else VATTN_FLAT8(_Float16, false); }
+    else { if (vec) VATTN_FLAT8(__bf16, true); else VATTN_FLAT8(__bf16, false); }
+#undef VATTN_FLAT8
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
     return VATTN_K_OK;

@@ -43,15 +43,42 @@ constexpr int DC_BN = 32;     // keys per wave tile
 // base = Lk - seqlen_q and draft key base + s iff bit s of tree_mask[b * seqlen_q + t] is set; is_causal is ignored.  The per-column bounds
 // of the masked tail tiles become a per-column bit mask, loaded there; the steady-state loop is the MT one.  The mask pointer is a kernel
 // argument of these builds alone (tree_mask_arg): vattn_attn_params is frozen, and the other builds keep their argument lists.
+// FP8: the K / V cache holds OCP e4m3 bytes with one fp32 scale per kv head (vattn_fp8kv_attn_with_kvcache, include/vattn_kernels.h; one-token
+// and MT builds without WIN / TREE / ROPE) — builds of their own, the others carry no trace of it.  q, P and the MFMAs stay T: the bytes are
+// widened in registers (exact: 3 mantissa bits, |x| <= 448) and the scales never touch an element — k_scale[hk] folds into sc, v_scale[hk] into
+// the final 1 / l, so partials are published scaled and the merges do not know the cache dtype.  A lane's 16-byte K load is 16 consecutive d of
+// one key row and feeds TWO k-steps: slot (g4, j) of k-step kk <-> d = 64*(kk/2) + 16*g4 + 8*(kk&1) + j (the dot product over d is order-free:
+// the Q^T fragments are loaded with the same permutation); V takes half the passes and is widened on its way into the wave-private LDS
+// layout, which the transposed reads and the PV MFMAs see unchanged.  No fused append, no fused rotation (the host quantises k_new / v_new
+// first: launch_append_fp8).  The scale pointers are a kernel argument of these builds alone, in the place of the TREE builds' mask.
 struct no_tree_mask {};
-template <bool TREE> using tree_mask_arg = std::conditional_t<TREE, const uint32_t*, no_tree_mask>;
-template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false>
+struct fp8_scales { const float* k; const float* v; };
+template <bool TREE, bool FP8 = false> using tree_mask_arg = std::conditional_t<TREE, const uint32_t*, std::conditional_t<FP8, fp8_scales, no_tree_mask>>;
+// 16 e4m3 bytes -> 16 values of T: lo = bytes 0-7, hi = bytes 8-15 (v_cvt_scalef32_pk_{f16,bf16}_fp8 with scale 1: two values per instruction)
+template <typename T> __device__ __forceinline__ void fp8_widen16(const uint4 x, uint4& lo, uint4& hi) {
+    const unsigned w[4] = {x.x, x.y, x.z, x.w};
+    unsigned r[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if constexpr (std::is_same_v<T, _Float16>) {
+            r[2 * i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, false));
+            r[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, true));
+        } else {
+            r[2 * i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, false));
+            r[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, true));
+        }
+    }
+    lo = make_uint4(r[0], r[1], r[2], r[3]);
+    hi = make_uint4(r[4], r[5], r[6], r[7]);
+}
+template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,
                                             const int item = -1, const int item_tb = 0, const int item_te = 0,
                                             const int st_mode = 0, const int st_slot = 0, const int st_lk = 0, const unsigned st_block = 0,
-                                            const int tstride = 1, const uint32_t* tree_mask = nullptr) {
+                                            const int tstride = 1, const uint32_t* tree_mask = nullptr, const fp8_scales scales = {}) {
     static_assert(!TREE || (MT && !WIN), "the tree mask belongs to the window-less multi-token builds");
+    static_assert(!FP8 || (!WIN && !TREE && ROPE == 0 && W == DC_WAVES && USE_TR), "the fp8 cache builds: one-token and multi-token, no window / tree mask / rotation");
     // st_mode != 0: a piece [item_tb, item_te) of the device-planned stream decomposition (decode_stream_kernel below).  Slot and visible
     // length come from the workgroup's plan (LDS) instead of two dependent global loads; st_mode 1 = the piece is the whole sequence: the
     // final rows are written; st_mode 2 = a partial, published as one record block at byte offset st_block of the workspace (16-byte
@@ -60,7 +87,10 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     using V8 = typename X::v8;
     constexpr int KK = HD / 32;          // k-steps of S^T (16x16x32)
     constexpr int DB = HD / 16;          // 16-wide d blocks of O^T
-    constexpr int CPR = HD / 8;          // 16-byte chunks per row
+    constexpr int CPR = FP8 ? HD / 16 : HD / 8;          // 16-byte chunks per row
+    constexpr int KL = FP8 ? KK / 2 : KK;                // 16-byte K loads per lane and 16-row block
+    using KVT = std::conditional_t<FP8, uint8_t, T>;     // a cache element
+    constexpr unsigned KVB = sizeof(KVT);
     constexpr int VPASS = (DC_BN * CPR) / 64;
     constexpr int V_WAVE_BYTES = DC_BN * HD * 2;        // [d/16][32 keys][16 d] sub-tiles, 32-byte rows
     constexpr int VSUB = DC_BN * 32;
@@ -105,10 +135,10 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     // cache (flash_attn_interface.py:1168-1176: append, then attend).  No inter-workgroup ordering is needed.
     const int new_key = fused_append ? Lk - 1 : -1;
 
-    const T* kbase = (const T*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)hk * p.k_head_stride;
-    const T* vbase = (const T*)p.v_cache + (int64_t)slot * p.v_batch_stride + (int64_t)hk * p.v_head_stride;
+    const KVT* kbase = (const KVT*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)hk * p.k_head_stride;
+    const KVT* vbase = (const KVT*)p.v_cache + (int64_t)slot * p.v_batch_stride + (int64_t)hk * p.v_head_stride;
 
-    // Q^T fragments (B operand, n = query head): slot (g4, j) <-> d = 32*kk + 8*g4 + j
+    // Q^T fragments (B operand, n = query head): slot (g4, j) <-> d = 32*kk + 8*g4 + j (FP8: d = 64*(kk/2) + 16*g4 + 8*(kk&1) + j, see above)
     V8 qf[NB][KK];
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) {
@@ -121,6 +151,9 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
 #pragma unroll
         for (int kk = 0; kk < KK; kk++) {
             uint4 v = make_uint4(0, 0, 0, 0);
+            if constexpr (FP8) {
+                if (row_head < R) v = *(const uint4*)(qptr + 64 * (kk / 2) + 8 * (kk & 1) + 16 * g4);
+            } else
             if (row_head < R) v = *(const uint4*)(qptr + 32 * kk + 8 * g4);
             qf[nb][kk] = as_v8<V8>(v);
         }
@@ -162,13 +195,15 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
         m_run[nb] = -INFINITY;
         l_run[nb] = 0.f;
     }
-    const float sc = p.softmax_scale * kLog2e;
+    float sm_scale = p.softmax_scale;                    // FP8: k_scale[hk] folded in (scores = q . stored * k_scale)
+    if constexpr (FP8) sm_scale *= scales.k[hk];
+    const float sc = sm_scale * kLog2e;
     char* vsm = smem + wave * V_WAVE_BYTES;
 
-    uint4 kreg[PF][2][KK], vreg[PF][VPASS];
-    const unsigned k_rs_bytes = (unsigned)p.k_row_stride * 2u, v_rs_bytes = (unsigned)p.v_row_stride * 2u;
-    const T* kbase_u = uniform_ptr(kbase);
-    const T* vbase_u = uniform_ptr(vbase);
+    uint4 kreg[PF][2][KL], vreg[PF][VPASS];
+    const unsigned k_rs_bytes = (unsigned)p.k_row_stride * KVB, v_rs_bytes = (unsigned)p.v_row_stride * KVB;
+    const KVT* kbase_u = uniform_ptr(kbase);
+    const KVT* vbase_u = uniform_ptr(vbase);
     // per-lane byte offsets inside a tile: ONE live register each; the row groups of the further instructions are wave-uniform
     // multiples of the row stride added per instruction (in the VGPR offset: the instruction's scalar offset is EXCLUDED from the
     // descriptor's bounds check, and the bound is what keeps the loads off unmapped pages), the k-steps travel in the immediate
@@ -189,12 +224,13 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
 #pragma unroll
         for (int kb = 0; kb < 2; kb++)
 #pragma unroll
-            for (int kk = 0; kk < KK; kk++) kreg[u][kb][kk] = buf_load16(kr, ko + (unsigned)kb * k_kb_step + 64u * kk);
+            for (int kk = 0; kk < KL; kk++) kreg[u][kb][kk] = buf_load16(kr, ko + (unsigned)kb * k_kb_step + 64u * kk);
 #pragma unroll
         for (int ps = 0; ps < VPASS; ps++) vreg[u][ps] = buf_load16(vr, vo + (unsigned)ps * v_ps_step);
     };
     // the new K/V row (fused append) replaces its row of the LAST tile in registers; the gb == 0 workgroup also stores it
     auto substitute_new_row = [&](int k0) {      // (register set 0: the last tile is loaded there)
+      if constexpr (!FP8) {
         const T* kn = (const T*)p.k_new + (int64_t)b * p.knew_batch_stride + (int64_t)hk * p.knew_head_stride;
         const T* vn = (const T*)p.v_new + (int64_t)b * p.vnew_batch_stride + (int64_t)hk * p.vnew_head_stride;
         T* kc = (T*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)hk * p.k_head_stride + (int64_t)new_key * p.k_row_stride;
@@ -230,6 +266,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                 if (gb == 0 && new_key < p.seqlen_k) *(uint4*)(vc + (idx % CPR) * 8) = v;
             }
         }
+      }
     };
     // One 32-key tile of this wave: V registers -> wave-private LDS, S^T = K.Q^T on the register-resident K fragments, request the
     // wave's next tile into the freed registers, online softmax, O^T += V^T.P^T.  RAGGED: the sequence's last tile (keys at or
@@ -243,10 +280,34 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
         for (int ps = 0; ps < VPASS; ps++) {
             const int idx = ps * 64 + lane;
             const int row = idx / CPR, c = idx % CPR;
-            *(uint4*)(vsm + (c >> 1) * VSUB + row * 32 + ((c & 1) << 4)) = vreg[u][ps];
+            if constexpr (FP8) {      // chunk c = 16 d of one key = one 32-byte row of sub-tile c
+                uint4 lo, hi;
+                fp8_widen16<T>(vreg[u][ps], lo, hi);
+                *(uint4*)(vsm + c * VSUB + row * 32) = lo;
+                *(uint4*)(vsm + c * VSUB + row * 32 + 16) = hi;
+            } else {
+                *(uint4*)(vsm + (c >> 1) * VSUB + row * 32 + ((c & 1) << 4)) = vreg[u][ps];
+            }
         }
         // ---- S^T = K.Q^T (every head block of the group uses the same K fragments) ----
         f32x4 s[NB][2];
+        if constexpr (FP8) {      // a load is widened ONCE and feeds the k-steps 2 kp, 2 kp + 1 of every head block
+#pragma unroll
+            for (int kb = 0; kb < 2; kb++) {
+#pragma unroll
+                for (int nb = 0; nb < NB; nb++) s[nb][kb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kp = 0; kp < KL; kp++) {
+                    uint4 lo, hi;
+                    fp8_widen16<T>(kreg[u][kb][kp], lo, hi);
+#pragma unroll
+                    for (int nb = 0; nb < NB; nb++) {
+                        s[nb][kb] = X::mfma16(as_v8<V8>(lo), qf[nb][2 * kp], s[nb][kb]);
+                        s[nb][kb] = X::mfma16(as_v8<V8>(hi), qf[nb][2 * kp + 1], s[nb][kb]);
+                    }
+                }
+            }
+        } else {
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) {
             V8 qt[KK];
@@ -264,6 +325,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
 #pragma unroll
                 for (int kk = 0; kk < KK; kk++) s[nb][kb] = X::mfma16(as_v8<V8>(kreg[u][kb][kk]), qt[kk], s[nb][kb]);
             }
+        }
         }
         // request the wave's next tile while this one is being consumed (past the end: every lane out of range, no access)
         if (!RAGGED) load_tile(u, next_tile);
@@ -413,7 +475,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     }
     if (own_last) {
         load_tile(0, tail_tile);
-        if (!MT && fused_append) substitute_new_row(tail_tile * DC_BN);
+        if (!MT && !FP8 && fused_append) substitute_new_row(tail_tile * DC_BN);
         process_tile(std::true_type{}, 0, tail_tile, ntiles_total);
     }
 
@@ -461,7 +523,8 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                 }
                 const int tq = MT ? rh / G : 0;                   // column -> (token, head)
                 const int hh = hk * G + rh - tq * G;
-                const float inv = (lsum == 0.f || lsum != lsum) ? 1.f : 1.f / lsum;
+                float inv = (lsum == 0.f || lsum != lsum) ? 1.f : 1.f / lsum;
+                if constexpr (FP8) inv *= scales.v[hk];      // (partials are published scaled: the merges do not know the cache dtype)
 #pragma unroll
                 for (int e = 0; e < 4; e++) acc[e] *= inv;
                 if (st_mode == 1) {
@@ -470,7 +533,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                     for (int e = 0; e < 4; e++) o4[e] = X::cvt(acc[e]);
                     *(typename X::v4*)((T*)p.out + (int64_t)b * p.o_batch_stride + (MT ? (int64_t)tq * p.o_row_stride : 0) + (int64_t)hh * p.o_head_stride + d0) = o4;
                     if (p.softmax_lse && d0 == 0)
-                        p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * p.softmax_scale + __logf(lsum));
+                        p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * sm_scale + __logf(lsum));
                 } else {
                     // record block: float o[16 * NB][HD], then float lse[16 * NB] (log2 domain) — see decode_stream_kernel
                     const unsigned r16 = (unsigned)(nb * 16 + row);
@@ -500,11 +563,12 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
             }
             const int tq = MT ? rh / G : 0;                       // column -> (token, head)
             const int hh = hk * G + rh - tq * G;
-            const float inv = (lsum == 0.f || lsum != lsum) ? 1.f : 1.f / lsum;
+            float inv = (lsum == 0.f || lsum != lsum) ? 1.f : 1.f / lsum;
+            if constexpr (FP8) inv *= scales.v[hk];
             if (num_splits == 1 && item < 0) {
                 ((T*)p.out)[(int64_t)b * p.o_batch_stride + (MT ? (int64_t)tq * p.o_row_stride : 0) + (int64_t)hh * p.o_head_stride + d] = X::cvt(acc * inv);
                 if (p.softmax_lse && d == 0)
-                    p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * p.softmax_scale + __logf(lsum));
+                    p.softmax_lse[MT ? ((int64_t)b * p.h + hh) * p.seqlen_q + tq : (int64_t)b * p.h + hh] = (lsum == 0.f) ? INFINITY : (mx * sm_scale + __logf(lsum));
             } else {
                 float* oacc = (float*)p.workspace;
                 // (MT: combine_kernel's layout for seqlen_q rows per entry: partial rows [split][b][token][head])
@@ -751,10 +815,12 @@ __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, 
 
 // nwg: workgroups per (kv head, group) = gridDim.x.  The partials are merged by decode_stream_combine_kernel in a second launch (merging
 // inside the launch, XCD-consecutive ranges, per-workgroup clock stamps, fair-share issue priority: tools/lab/csrc/decode_body_lab.h).
-template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false>
-__global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append, tree_mask_arg<TREE> tree_mask = {}) {
+template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
+__global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append, tree_mask_arg<TREE, FP8> tree_mask = {}) {
     const uint32_t* tmask = nullptr;
     if constexpr (TREE) tmask = tree_mask;
+    fp8_scales scales = {};
+    if constexpr (FP8) scales = tree_mask;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_plan[3 * DC_MAXB];                // stream mode: the plan, for the pieces after the first
     const int tid = threadIdx.x;
@@ -823,7 +889,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     for (;;) {
         const unsigned blk = stream_table_bytes(p.b) + (((unsigned)(w + b) * p.h_k + hk) * gblocks + gb) * RB;
         if (tb == 0 && hk == 0 && gb == 0 && tid == 0) stream_publish_seq(p, b, first_rec, cnt);      // (the owner of the sequence's first piece)
-        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT, TREE>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk, 1, tmask);
+        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT, TREE, FP8>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk, 1, tmask, scales);
         if (geo.uniform || !next_piece(b + 1)) return;
         __syncthreads();                                 // the previous piece's in-workgroup merge is done with the LDS
     }
@@ -842,13 +908,15 @@ __global__ __launch_bounds__(256) void decode_stream_combine_kernel(vattn_attn_p
 
 // gblocks = head-block GROUPS per kv head (ceil(ceil(G/16) / NB)).  The partials of a split launch are merged by combine_kernel in a
 // second launch (the single-launch merges live in the lab copy).
-template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false, bool TREE = false>
-__global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append, tree_mask_arg<TREE> tree_mask = {}) {
+template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
+__global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append, tree_mask_arg<TREE, FP8> tree_mask = {}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const uint32_t* tmask = nullptr;
     if constexpr (TREE) tmask = tree_mask;
+    fp8_scales scales = {};
+    if constexpr (FP8) scales = tree_mask;
     int split, hk, gb, b;
-    if (!MT && p.split_items != nullptr) {          // (host items: the one-token form only)
+    if (!MT && !FP8 && p.split_items != nullptr) {          // (host items: the one-token form only, 2-byte caches only)
         // length-balanced plan: blockIdx.x = work item (a piece of ONE sequence), blockIdx.y = (kv head, head-block group)
         const vattn_decode_item it = p.split_items[blockIdx.x];
         decode_body<T, HD, USE_TR, NB, W, PF, -1, WIN>(p, 2, gblocks, fused_append, it.index_in_seq, blockIdx.y / gblocks, blockIdx.y % gblocks, it.b, smem,
@@ -874,8 +942,8 @@ __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB >
         gb = blockIdx.y % gblocks;
         b = blockIdx.z;
     }
-    decode_body<T, HD, USE_TR, NB, W, PF, MT ? 0 : -1, WIN, MT, TREE>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
-                                          (decode_striped(p) && num_splits > 1) ? num_splits : 1, tmask);
+    decode_body<T, HD, USE_TR, NB, W, PF, (MT || FP8) ? 0 : -1, WIN, MT, TREE, FP8>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
+                                          (decode_striped(p) && num_splits > 1) ? num_splits : 1, tmask, scales);
 }
 
 }  // namespace vattn_k

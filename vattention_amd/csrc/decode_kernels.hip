@@ -208,40 +208,51 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
 // (DC_WAVES x 8 KiB) — and where the new K/V rows are written: by the attention kernel itself (fused_append: ONE new row, not the multi-token
 // form), else by a separate append launch in front of it on the same stream (seqlen_knew > 1; the multi-token form, which has no fused
 // rotation either).
+// What travels BESIDE the parameter block (vattn_attn_params is frozen): the mask words of the tree-masked call, the per-kv-head scales of a
+// call over an fp8 cache (decode_body.h: TREE, FP8)
+struct decode_extra { const uint32_t* tree_mask; const float* k_scale; const float* v_scale; };
 struct decode_launch { size_t smem; int fused_append; };
-template <int HD, bool MT> static decode_launch begin_decode_launch(const vattn_attn_params* p, hipStream_t st) {
-    const int fused_append = (!MT && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
-    if (p->k_new && !fused_append) launch_append(p, st);
+// FP8: no fused append — the new rows are quantised by the append launch (cache_kernels.hip, launch_append_fp8), whatever their count
+template <int HD, bool MT, bool FP8> static decode_launch begin_decode_launch(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    const int fused_append = (!MT && !FP8 && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
+    if (p->k_new && !fused_append) {
+        if constexpr (FP8) launch_append_fp8(p, x.k_scale, x.v_scale, st);
+        else launch_append(p, st);
+    }
     return {(size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2, fused_append};
 }
-// The last kernel argument of every build: the mask words of the TREE builds, an empty struct for the others (decode_body.h, tree_mask_arg)
-template <bool TREE> static tree_mask_arg<TREE> mask_arg(const uint32_t* tree_mask) {
-    if constexpr (TREE) return tree_mask; else return {};
+// The last kernel argument of every build: the mask words of the TREE builds, the scale pointers of the FP8 builds, an empty struct for the
+// others (decode_body.h, tree_mask_arg)
+template <bool TREE, bool FP8> static tree_mask_arg<TREE, FP8> mask_arg(const decode_extra& x) {
+    if constexpr (TREE) return x.tree_mask;
+    else if constexpr (FP8) return fp8_scales{x.k_scale, x.v_scale};
+    else return {};
 }
 
 // WIN: the sliding-window builds (decode_body.h) — taken iff the block carries a window, so a window-less call runs the kernels it always ran
 // MT: the multi-token builds — no fused append, no fused rotation (ROPE 0)
 // TREE: the tree-masked builds of the multi-token form (decode_body.h) — the same plan, grid and workspace; the mask is their extra argument
-template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const uint32_t* tree_mask) {
+// FP8: the builds that read an e4m3 cache (decode_body.h) — the same plan, grid, workspace and merges; the scales are their extra argument
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const decode_extra& x) {
     if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
     if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
-    const decode_launch l = begin_decode_launch<HD, MT>(p, st);
+    const decode_launch l = begin_decode_launch<HD, MT, FP8>(p, st, x);
     const dim3 grid((unsigned)nwg, (unsigned)p->h_k), block(64 * DC_WAVES);
-    auto kernel = decode_stream_kernel<T, HD, true, NB, MT ? 0 : -1, WIN, MT, TREE>;
-    if constexpr (!MT && __is_same(T, __bf16)) {
+    auto kernel = decode_stream_kernel<T, HD, true, NB, (MT || FP8) ? 0 : -1, WIN, MT, TREE, FP8>;
+    if constexpr (!MT && !FP8 && __is_same(T, __bf16)) {
         // bf16 rotates through fp32 (no packed arithmetic): with the fused-RoPE path compiled in, decode_stream_kernel<bf16, 128, one head block> is
         // 12 registers over the 168 of three workgroups per CU and gets a scratch segment — 9 us per launch even when no rotation is asked for
         // (profiles/r06_decode_bf16_scratch.txt).  Two builds: without the path (what the reference's wrapper calls: no spill), and the one that
         // takes it at run time (the path compiled in UNCONDITIONALLY spills more: 46 registers instead of 12).
-        if (!p->rotary_cos_sin) kernel = decode_stream_kernel<T, HD, true, NB, 0, WIN, MT, TREE>;
+        if (!p->rotary_cos_sin) kernel = decode_stream_kernel<T, HD, true, NB, 0, WIN, MT, TREE, FP8>;
     }
-    hipLaunchKernelGGL(kernel, grid, block, l.smem, st, *p, 1, l.fused_append, mask_arg<TREE>(tree_mask));
+    hipLaunchKernelGGL(kernel, grid, block, l.smem, st, *p, 1, l.fused_append, mask_arg<TREE, FP8>(x));
     hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB, MT>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
     return launch_status();
 }
 
-template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
-    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT, TREE>(p, st, nwg, tree_mask);
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT, TREE, FP8>(p, st, nwg, x);
     const int groups = decode_groups(p);
     const bool planned = p->split_items != nullptr;
     if (planned && (!p->split_seq || p->num_split_items <= 0)) return fail(VATTN_K_ERR_INVALID, "split_items needs split_seq and num_split_items");
@@ -253,8 +264,8 @@ template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE> int launch_d
         const long w = (long)splits * p->h_k * p->b;
         grid = dim3((unsigned)(((w + 7) / 8) * 8 * groups));
     }
-    const decode_launch l = begin_decode_launch<HD, MT>(p, st);
-    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT, TREE>), grid, block, l.smem, st, *p, splits, groups, l.fused_append, mask_arg<TREE>(tree_mask));
+    const decode_launch l = begin_decode_launch<HD, MT, FP8>(p, st, x);
+    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT, TREE, FP8>), grid, block, l.smem, st, *p, splits, groups, l.fused_append, mask_arg<TREE, FP8>(x));
     const int sq = MT ? p->seqlen_q : 1;
     if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, *p);
     else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * sq * p->h), dim3(128), 0, st, *p, splits, sq);
@@ -263,26 +274,31 @@ template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE> int launch_d
 
 // The builds a block takes, from the top: TREE (vattn_tree_attn_with_kvcache: the caller checked multitoken_form(p) and that the block carries
 // no window — the multi-token launch of the same block, planners, grids, append and merges, on the TREE builds), else one token or the
-// multi-token form (the caller checked multitoken_form(p)), with or without a window; then one or two head blocks per workgroup.
-template <typename T, int HD, bool WIN, bool MT, bool TREE> int launch_decode_w(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
-    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, WIN, MT, TREE>(p, st, tree_mask) : launch_decode_nb<T, HD, 1, WIN, MT, TREE>(p, st, tree_mask);
+// multi-token form (the caller checked multitoken_form(p)), with or without a window; then one or two head blocks per workgroup.  FP8
+// (vattn_fp8kv_attn_with_kvcache: the caller checked its gate — decode_form(p), no window): one token or the multi-token form on the FP8 builds.
+template <typename T, int HD, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_w(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, WIN, MT, TREE, FP8>(p, st, x) : launch_decode_nb<T, HD, 1, WIN, MT, TREE, FP8>(p, st, x);
 }
-template <typename T, int HD, bool TREE> int launch_decode_t(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
-    if constexpr (TREE) return launch_decode_w<T, HD, false, true, true>(p, st, tree_mask);
+template <typename T, int HD, bool TREE, bool FP8> int launch_decode_t(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    if constexpr (TREE) return launch_decode_w<T, HD, false, true, true, false>(p, st, x);
+    else if constexpr (FP8) return p->seqlen_q == 1 ? launch_decode_w<T, HD, false, false, false, true>(p, st, x) : launch_decode_w<T, HD, false, true, false, true>(p, st, x);
     else {
         const bool win = p->window_left_plus1 > 0;
-        if (p->seqlen_q == 1) return win ? launch_decode_w<T, HD, true, false, false>(p, st, nullptr) : launch_decode_w<T, HD, false, false, false>(p, st, nullptr);
-        return win ? launch_decode_w<T, HD, true, true, false>(p, st, nullptr) : launch_decode_w<T, HD, false, true, false>(p, st, nullptr);
+        if (p->seqlen_q == 1) return win ? launch_decode_w<T, HD, true, false, false, false>(p, st, x) : launch_decode_w<T, HD, false, false, false, false>(p, st, x);
+        return win ? launch_decode_w<T, HD, true, true, false, false>(p, st, x) : launch_decode_w<T, HD, false, true, false, false>(p, st, x);
     }
 }
-// dtype x head dimension: the one ladder of both entry points
-template <bool TREE> static int launch_decode_dtype_hd(const vattn_attn_params* p, hipStream_t st, const uint32_t* tree_mask) {
+// dtype x head dimension: the one ladder of the three entry points
+template <bool TREE, bool FP8> static int launch_decode_dtype_hd(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
     const bool f16 = p->dtype == VATTN_DTYPE_F16;
-    if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64, TREE>(p, st, tree_mask) : launch_decode_t<__bf16, 64, TREE>(p, st, tree_mask);
-    return f16 ? launch_decode_t<_Float16, 128, TREE>(p, st, tree_mask) : launch_decode_t<__bf16, 128, TREE>(p, st, tree_mask);
+    if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64, TREE, FP8>(p, st, x) : launch_decode_t<__bf16, 64, TREE, FP8>(p, st, x);
+    return f16 ? launch_decode_t<_Float16, 128, TREE, FP8>(p, st, x) : launch_decode_t<__bf16, 128, TREE, FP8>(p, st, x);
 }
-int launch_decode_form(const vattn_attn_params* p, hipStream_t st) { return launch_decode_dtype_hd<false>(p, st, nullptr); }
-int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) { return launch_decode_dtype_hd<true>(p, st, tree_mask); }
+int launch_decode_form(const vattn_attn_params* p, hipStream_t st) { return launch_decode_dtype_hd<false, false>(p, st, {nullptr, nullptr, nullptr}); }
+int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) { return launch_decode_dtype_hd<true, false>(p, st, {tree_mask, nullptr, nullptr}); }
+int launch_fp8kv_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st) {
+    return launch_decode_dtype_hd<false, true>(p, st, {nullptr, k_scale, v_scale});
+}
 
 // Length-balanced split of a ragged decode batch (include/vattn_kernels.h, vattn_decode_plan).  Every sequence is cut into pieces of at
 // most T tiles; T is the smallest piece length for which the pieces of ALL sequences fit the resident workgroups in one round

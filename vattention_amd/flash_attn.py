@@ -180,21 +180,25 @@ def relaunch(p, q_ptr: int, k_new_ptr: int, v_new_ptr: int, out_ptr: int, k_cach
     _issue(p, dev, *fast)
 
 
-def _issue(p, dev, lib, need=None, mask=None):
+def _issue(p, dev, lib, need=None, mask=None, scales=None):
     """The one launch: the workspace the call needs (asked of the library unless `need` is known: relaunch) from the per-(device, stream)
-    cache, the call on the current stream — the tree-masked entry point iff `mask` is given — and its return code as an exception (the
-    tree entry's -10 names the rule of its gate that the block breaks: NotImplementedError).  Returns the workspace need."""
+    cache, the call on the current stream — the tree-masked entry point iff `mask` is given, the fp8-cache entry point iff `scales` =
+    (k_scale, v_scale; either may be None: the library refuses that) — and its return code as an exception (the -10 of those two entries
+    names the rule of their gate that the block breaks: NotImplementedError).  Returns the workspace need."""
     if need is None:
-        need = (lib.vattn_attn_workspace_bytes if mask is None else lib.vattn_tree_attn_workspace_bytes)(C.byref(p))
+        need = (lib.vattn_tree_attn_workspace_bytes if mask is not None else lib.vattn_fp8kv_attn_workspace_bytes if scales is not None
+                else lib.vattn_attn_workspace_bytes)(C.byref(p))
     st = K.current_stream_ptr(dev)
     if need:
         p.workspace = _workspace(need, dev, st).data_ptr()   # kept alive by the per-(device, stream) cache until a larger one replaces it
-    if mask is None:
-        rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
-    else:
+    if mask is not None:
         rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
+    elif scales is not None:
+        rc = lib.vattn_fp8kv_attn_with_kvcache(C.byref(p), *(s.data_ptr() if s is not None else None for s in scales), st)
+    else:
+        rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
     if rc != 0:
-        raise (NotImplementedError if mask is not None and rc == -10 else RuntimeError)(K.last_error(lib))
+        raise (NotImplementedError if (mask is not None or scales is not None) and rc == -10 else RuntimeError)(K.last_error(lib))
     return need
 
 
@@ -219,7 +223,11 @@ def _check_cuda(*ts):
             raise RuntimeError("vattention_amd.flash_attn: tensors must live on the GPU (there is no CPU path)")
 
 
-def _check_dtypes(q, k_cache, v_cache):
+def _check_dtypes(q, k_cache, v_cache, cache_dtype=None):
+    if cache_dtype is not None:          # (the fp8-cache entry: q / k / v keep the I/O dtype, the caches have their own)
+        if k_cache.dtype != cache_dtype or v_cache.dtype != cache_dtype:
+            raise RuntimeError("k_cache and v_cache must have dtype %s" % cache_dtype)
+        return
     if k_cache.dtype != q.dtype:
         raise RuntimeError("query and key must have the same dtype")
     if v_cache.dtype != q.dtype:
@@ -256,7 +264,7 @@ def _set_scalars(p, q, num_splits, softmax_scale):
     p.softmax_scale = float(q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale)
 
 
-def _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse):
+def _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse, cache_dtype=None):
     """The shared front half of the [B, Sq, Hq, D]-query entry points: argument checks (wording as flash_api.cpp), `out` / LSE, and an
     AttnParams with its tensor, stride and shape fields filled.  Returns (block, the tensors it points to — to be kept alive —,
     out, lse, (B, Sq, Sk, Sn, D), device); in the tuple, cache_seqlens / cache_batch_idx are the normalised int32 tensors."""
@@ -267,7 +275,7 @@ def _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out,
     q, k, v = mc(q), mc(k), mc(v)
     B, Sq, Hq, D = q.shape
     Bc, Sk, Hkv, Dk = k_cache.shape
-    _check_dtypes(q, k_cache, v_cache)
+    _check_dtypes(q, k_cache, v_cache, cache_dtype)
     dev = q.device
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=dev)
@@ -414,6 +422,29 @@ def flash_attn_tree_with_kvcache(q, k_cache, v_cache, tree_mask, k=None, v=None,
     return (out, lse) if return_softmax_lse else out
 
 
+def flash_attn_fp8kv_with_kvcache(q, k_cache, v_cache, k_scale, v_scale, k=None, v=None, cache_seqlens: Optional[Union[int, torch.Tensor]] = None,
+                                  cache_batch_idx: Optional[torch.Tensor] = None, softmax_scale=None, causal=False, return_softmax_lse=False,
+                                  out=None, _num_splits: int = 0, _variant: int = 0):
+    """MI355X extension (include/vattn_kernels.h, "FP8 KV cache"): decode over a float8_e4m3fn cache with one fp32 scale per kv head.  q
+    [B, 1, Hq, D] or the multi-token form [B, 2..8, Hq, D] (fp16 / bf16, also the dtype of out and of k / v); k_cache / v_cache
+    [Bc, rows, Hkv, D] float8_e4m3fn (any strided view whose strides are multiples of 16); k_scale / v_scale float32 [Hkv] GPU tensors,
+    value = stored * scale — read by the kernels, never by the host: works under graph capture like decode.  `k` / `v` are quantised and
+    appended at cache_seqlens first (cache_ops.cache_flat_fp8's bytes).  Half the K/V bytes of the 2-byte call; q and P are not
+    quantised.  There is no window, no fused rotary and no host plan on this path; a call outside the gate (the prefill form: more than
+    8 query rows, or seqlen_q * Hq / Hkv > 64) raises NotImplementedError with the library's message, which names the rule.  `_num_splits` < 0: the decode kernels' forced grids, `_variant`: the product's A/B selectors (tests, tools/kbench.py)."""
+    p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse,
+                                                              cache_dtype=torch.float8_e4m3fn)
+    for s in (k_scale, v_scale):
+        if s is not None and (not s.is_cuda or s.dtype != torch.float32 or s.shape != (p.h_k,) or not s.is_contiguous()):
+            raise RuntimeError("k_scale / v_scale must be contiguous float32 [num_kv_heads] GPU tensors")
+    p.is_causal = 1 if causal else 0
+    _set_scalars(p, keep[0], _num_splits, softmax_scale)
+    p.variant = int(_variant)
+    _issue(p, dev, K.klib(), None, None, (k_scale, v_scale))      # (the product library only; a block outside the gate is refused by the call)
+    counters["fp8kv_decode_calls"] += 1
+    return (out, lse) if return_softmax_lse else out
+
+
 def _lengths_from_page_manager(k_cache, B: int):
     """Visible tokens of the B row-blocks of `k_cache` according to the page manager's last step (vattention.resolve_view), or None."""
     from . import vattention as _va
@@ -435,7 +466,7 @@ _plan_cache = {}      # (shapes, lengths, device, stream) -> _PrefillPlan; a few
 # with other lengths in between gets plans sized for the wrong lengths; False switches the lookup off (the view's row count then bounds
 # the plan, FlashAttention's own rule).
 USE_PAGE_MANAGER_LENGTHS = True
-counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
+counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "fp8kv_decode_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
 
 
 def _cached_prefill_plan(p, klens, dev):
