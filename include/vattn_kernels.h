@@ -262,7 +262,7 @@ int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, 
 
 /* FP8 KV CACHE (OCP e4m3): halves the K/V bytes a decode step reads, doubles the tokens per physical page.  Additive: vattn_attn_params and
  * VATTN_KERNELS_ABI are unchanged, the scale pointers travel BESIDE the parameter block as extra arguments of builds of the decode kernels
- * of their own; every other kernel and entry point is what it was.
+ * — and of the register-staged prefill kernels: "Prefill over an fp8 cache" below — of their own; every other kernel and entry point is what it was.
  * STORAGE: OCP float8_e4m3fn, one byte per element, caches of the usual shape [batch_cache, rows, h_k, d]; last dimension contiguous, the
  * other strides multiples of 16 elements (16-byte chunks).  SCALES: k_scale, v_scale are DEVICE float32[h_k], positive and finite; the host
  * never dereferences them (calls stay graph-capturable).  value = stored * scale.
@@ -297,6 +297,26 @@ int vattn_cache_flat_fp8(const void* key, const void* value, void* k_cache, void
 int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream);
 size_t vattn_fp8kv_attn_workspace_bytes(const vattn_attn_params* p);
 int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
+
+/* Prefill over an fp8 cache: chunk n of a prompt attends to chunks 0 .. n-1 as the fp8 bytes they were stored as.  Same conventions as the
+ * decode call above (p->dtype, strides in bytes, device scales, stride / alignment rules).  Builds of their own of the register-staged
+ * prefill kernels (8 / 4 waves x 32 rows, d = 64 / 128, f16 / bf16): a 16-byte load is 16 consecutive d of one key, widened on its way
+ * into LDS — the LDS image is the 2-byte kernel's for the unscaled values, everything behind it is that kernel; k_scale[hk] folds into the
+ * softmax scale and the LSE, v_scale[hk] into the final 1 / l, also of the published fp32 partials (the merge does not know the dtype).
+ * APPEND: k_new / v_new are quantised into rows cache_seqlens[b] .. by an append launch in front of the attention launch on the same
+ * stream, so the chunk attends to its OWN keys AS STORED — exactly what a later decode step reads, not the 2-byte values it was given.
+ * GATE: the prefill form — every block the decode gate above does not take — causal or not, with or without cache_batch_idx, softmax_lse,
+ * batched chunks (q_start / q_lens; k_new then stays refused as everywhere: append with vattn_cache_flat_fp8 first).  Refused with
+ * VATTN_K_ERR_UNSUPPORTED and a message that names the rule: a decode-form block (call vattn_fp8kv_attn_with_kvcache), window_left_plus1 > 0,
+ * rotary_cos_sin, pf_items / pf_num_wg, split_items, explicit tiling 7 (prefill64 moves its tiles by LDS-DMA and has no fp8 build), d other
+ * than 64 / 128, a -DVATTN_LAB build.  NULL scales: VATTN_K_ERR_INVALID.
+ * PLAN: that of vattn_flash_attn_with_kvcache for the same block with its prefill64 branch skipped — tiling 1 or 4 and the split count
+ * those rules give, the same grid, workgroup order and workspace layout; nothing is tuned apart.  _workspace_bytes / _plan_describe answer
+ * what this call gets (0 / an error outside the gate).
+ * CONTRACT: as everywhere — no K/V load at or beyond Lk = cache_seqlens[b] + seqlen_knew. */
+int vattn_fp8kv_prefill_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream);
+size_t vattn_fp8kv_prefill_workspace_bytes(const vattn_attn_params* p);
+int vattn_fp8kv_prefill_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
 
 /* Fused prefill || decode for a hybrid batch (replaces the reference's POD-Attention entry point
  * /root/reference/pod_attn/pod_attn/flash_attn_interface.py true_fused_attn_with_kvcache, call site

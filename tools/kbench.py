@@ -5,7 +5,9 @@ usage: python tools/kbench.py [prefill] [decode] [--variant N]
        python tools/kbench.py multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base LIB] [--bf16] [--tree]   (the multi-token decode form;
                                                                           --tree: the tree-masked entry with a chain mask beside the causal call)
        python tools/kbench.py decode --kv-fp8 [--only NAMES] / multitoken --kv-fp8 --mt ...   (the same call over an fp8 (e4m3) cache —
-                                                                          vattn_fp8kv_attn_with_kvcache — beside the 2-byte call, alternating, over rotating caches)"""
+                                                                          vattn_fp8kv_attn_with_kvcache — beside the 2-byte call, alternating, over rotating caches)
+       python tools/kbench.py prefill --kv-fp8 [--only NAMES] [--bf16]   (a chunk on a prefix through vattn_fp8kv_prefill_with_kvcache beside the 2-byte call
+                                                                          forced to the same tiling and split, and the 2-byte call under its default plan)"""
 import ctypes as C
 import os
 import sys
@@ -228,6 +230,66 @@ def fp8_ab(name, B, sq, Hq, Hkv, ctx, slots, ragged=False):
     print("    ratio 2-byte / fp8 : %.2fx" % (m16 / m8), flush=True)
 
 
+def fp8_prefill_ab(name, Hq, Hkv, n, c):
+    """prefill --kv-fp8: ONE block — a causal chunk of n rows whose keys [0, c + n) are in the cache — timed three ways, ALTERNATING in one
+    process over R rotating caches (R x the 2-byte K/V bytes beyond the 256 MiB Infinity Cache, at most 24), warmed up, five windows each:
+    (a) vattn_fp8kv_prefill_with_kvcache over an fp8 (e4m3) cache of the same values; (b) the 2-byte call FORCED to (a)'s tiling and split
+    count — the yardstick of the fp8 builds: the same grid, the same kernel but for the staging; (c) the 2-byte call under its default plan
+    (prefill64 where the planner takes it): what a caller pays for prefill64 having no fp8 build."""
+    from vattention_amd.cache_ops import cache_flat_fp8
+    torch.manual_seed(0)
+    lib, st = K.klib(), torch.cuda.current_stream().cuda_stream
+    rows = c + n
+    by16 = 2.0 * rows * Hkv * 128 * 2
+    R = min(24, max(2, int(1.5e9 // by16) + 1))
+    cl = torch.tensor([rows], dtype=torch.int32, device=DEV)
+    q = torch.randn(1, n, Hq, 128, device=DEV, dtype=DTYPE)
+    ks = torch.full((Hkv,), 6.0 / 448.0, dtype=torch.float32, device=DEV)       # N(0,1) data: amax over 10^8 samples is below 6
+    vs = ks.clone()
+    pa, pb, pc = [], [], []
+    for _ in range(R):
+        kc, vc = torch.randn(1, rows, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(1, rows, Hkv, 128, device=DEV, dtype=DTYPE)
+        k8, v8 = torch.empty(1, rows, Hkv, 128, device=DEV, dtype=torch.float8_e4m3fn), torch.empty(1, rows, Hkv, 128, device=DEV, dtype=torch.float8_e4m3fn)
+        cache_flat_fp8(kc.view(-1, Hkv, 128), vc.view(-1, Hkv, 128), k8.view(-1, Hkv, 128), v8.view(-1, Hkv, 128), ks, vs)
+        p8, keep = params(q, k8, v8, cl)
+        da = K.describe_fp8kv_prefill(p8)
+        w = torch.empty(da["workspace_bytes"] // 4 + 1, dtype=torch.float32, device=DEV)      # (this call's own need: its plan has no prefill64)
+        p8.workspace = w.data_ptr()
+        pa.append((p8, keep + [w]))
+        pb.append(params(q, kc, vc, cl, splits=da["nsplit"], variant=da["tiling"] << 1))
+        pc.append(params(q, kc, vc, cl))
+    db, dc = K.describe(pb[0][0]), K.describe(pc[0][0])
+    assert (db["tiling"], db["nsplit"], db["workgroups"]) == (da["tiling"], da["nsplit"], da["workgroups"]), (da, db)
+    call16 = lambda pp: lib.vattn_flash_attn_with_kvcache(C.byref(pp), st)
+    call8 = lambda pp: lib.vattn_fp8kv_prefill_with_kvcache(C.byref(pp), ks.data_ptr(), vs.data_ptr(), st)
+    iters = max(1, 24 // R)
+
+    def window(call, ps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            for pp, _k in ps:
+                if call(pp) != 0:
+                    raise RuntimeError(K.last_error(lib))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / (iters * len(ps)) * 1e3
+    runs = ((call8, pa), (call16, pb), (call16, pc))
+    for call, ps in runs:                                       # warm-up: every cache of all three
+        window(call, ps)
+    t = [[], [], []]
+    for _rep in range(5):                                       # alternating windows
+        for i, (call, ps) in enumerate(runs):
+            t[i].append(window(call, ps))
+    med = [sorted(x)[2] for x in t]
+    fl = 4.0 * Hq * 128 * (n * c + n * (n + 1) / 2)
+    print("  %-26s n=%d c=%d Hq=%2d Hkv=%d, %s, %d rotating caches" % (name, n, c, Hq, Hkv, "bf16" if DTYPE == torch.bfloat16 else "fp16", R))
+    for tag, d, m, x in (("(a) fp8 cache            ", da, med[0], t[0]), ("(b) 2-byte, (a)'s plan   ", db, med[1], t[1]), ("(c) 2-byte, default plan ", dc, med[2], t[2])):
+        print("    %s tiling %d nsplit %d wg %4d : median %8.1f us  (5 windows: %s; spread %.1f%%)  %7.1f TFLOP/s" % (
+            tag, d["tiling"], d["nsplit"], d["workgroups"], m, " ".join("%.1f" % y for y in x), 100.0 * (max(x) - min(x)) / m, fl / m / 1e6))
+    print("    ratios: (a) / (b) = %.3f   (a) / (c) = %.3f   (b) / (c) = %.3f" % (med[0] / med[1], med[0] / med[2], med[1] / med[2]), flush=True)
+
+
 def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
     """The multi-token decode call (q [B, sq, Hq, 128] against `ctx` cached tokens, the sq new rows appended) on caches that ROTATE (as
     --rotate: the Infinity Cache serves no repeat): this tree, the one-token decode step of the same batch, the prefill form of the same
@@ -361,7 +423,14 @@ if __name__ == "__main__":
         sys.exit(0)
     what = [a for a in sys.argv[1:] if a in ("prefill", "decode")] or ["prefill", "decode"]
     torch.zeros(1, device=DEV)
-    if "prefill" in what:
+    if "prefill" in what and "--kv-fp8" in sys.argv:
+        print("== prefill (causal chunk n against c cached) over an fp8 (e4m3) cache and a 2-byte cache, D=128 ==")
+        for name, Hq, Hkv, n, c in [("yi6b chunk2k@30k", 32, 4, 2048, 30720), ("llama70b/tp8 chunk2k@30k", 8, 1, 2048, 30720), ("yi6b chunk4k@28k", 32, 4, 4096, 28672),
+                                    ("llama8b chunk512@8k", 32, 8, 512, 7680)]:
+            if (ONLY and not any(o.strip() in name for o in ONLY.split(","))) or (not ONLY and "chunk2k@30k" not in name):
+                continue
+            fp8_prefill_ab(name, Hq, Hkv, n, c)
+    elif "prefill" in what:
         for v in VARIANTS:
             print("-- prefill variant %d (order %s, tiling %s) --" % (v, ["XCD-grouped (default)", "block-major per head", "heaviest-first across heads", "XCD-grouped"][(v >> 5) & 3] + (", prefill64 build %d" % ((v >> 8) & 15) if (v >> 8) & 15 else ""), {0: "default plan", 1: "8 waves x 32 rows", 2: "4 waves x 64 rows", 3: "8 waves x 32 rows, LDS-DMA ring, in-wave software pipeline (prefill32)", 4: "4 waves x 32 rows", 6: "8 waves, hand-interleaved MFMA/VALU groups", 7: "4 waves x 64 rows, LDS-DMA ring, in-wave software pipeline (prefill64)"}[(v >> 1) & 7]))
             prefill(v)

@@ -43,7 +43,8 @@ UNROLL_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1000000"]
 # waits the hand-placed ones do not know about) silently breaks it, and the kernel sits at the SGPR / VGPR limits.  Its translation unit
 # is therefore compiled with the resource-usage remarks on, and the build FAILS when any instantiation of a guarded kernel spills.
 NO_SPILL_KERNELS = {"prefill64_kernels.hip": "prefill64",      # prefill64_kernel and its sliding-window build prefill64w_kernel
-                     "prefill64p_kernels.hip": "prefill64p_kernel", "decode_kernels.hip": "decode_"}
+                     "prefill64p_kernels.hip": "prefill64p_kernel", "decode_kernels.hip": "decode_",
+                     "prefill_kernels.hip": "prefill_fp8_kernel"}      # the builds over an fp8 cache: their widening must fit the 2-byte siblings' register budget
 # ... except: the bf16 build of decode_stream_kernel (d = 128, one head block) that takes the fused-RoPE path at run time — bf16 rotates through fp32,
 # 12 registers more than three workgroups per CU leave; calls without rotation get the build without that path (decode_kernels.hip,
 # launch_decode_stream).  A scratch segment costs ~9 us per launch (profiles/r06_decode_bf16_scratch.txt): no other kernel may grow one unnoticed.

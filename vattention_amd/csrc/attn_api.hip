@@ -318,6 +318,33 @@ static const char* fp8kv_gate_reason(const vattn_attn_params* p) {
     return nullptr;
 }
 
+// ... and of the PREFILL form over an fp8 cache (vattn_fp8kv_prefill_with_kvcache): every block that decode_form() rejects, on the register-staged
+// prefill kernels (prefill_body.h, FP8) under the default launch — no window, rotation, host plan or prefill64 there
+static const char* fp8kv_prefill_gate_reason(const vattn_attn_params* p) {
+    if (kLab) return "the measurement build has no fp8 KV cache kernels (use libvattn_amd.so)";
+    if (p->window_left_plus1 > 0) return "an fp8 KV cache cannot be combined with a sliding window (window_left_plus1 > 0)";
+    if (p->rotary_cos_sin) return "an fp8 KV cache cannot be combined with fused rotary embedding (rotary_cos_sin): rotate q and k first";
+    if (p->split_items) return "an fp8 KV cache cannot be combined with split_items (host item plan)";
+    if (p->pf_items || p->pf_num_wg) return "fp8 prefill cannot be combined with pf_items / pf_num_wg (prefill work lists run on prefill64, which has no fp8 build)";
+    if (((p->variant >> 1) & 7) == 7) return "fp8 prefill: explicit tiling 7 is refused — prefill64 has no fp8 build (its tiles move by LDS-DMA and cannot be widened in flight)";
+    if (p->d != 64 && p->d != 128) return "fp8 prefill supports head dimensions 64 and 128";
+    if (decode_form(p)) return "fp8 prefill: this block takes the decode form (seqlen_q == 1 or the multi-token form) — call vattn_fp8kv_attn_with_kvcache";
+    return nullptr;
+}
+
+// The argument rules both calls over an fp8 cache add to validate(): the scales, whole 16-byte chunks of BYTES in the caches, aligned new rows
+static int fp8kv_check_args(const vattn_attn_params* p, const float* k_scale, const float* v_scale) {
+    if (!k_scale || !v_scale) return fail(VATTN_K_ERR_INVALID, "an fp8 KV cache needs k_scale and v_scale (device float32[h_k])");
+    const int64_t strides[] = {p->k_batch_stride, p->k_row_stride, p->k_head_stride, p->v_batch_stride, p->v_row_stride, p->v_head_stride};
+    for (int64_t s : strides)
+        if (s % 16 != 0) return fail(VATTN_K_ERR_UNSUPPORTED, "fp8 cache strides must be multiples of 16 elements (16-byte vector access)");
+    if (p->k_new && (((p->knew_batch_stride | p->knew_row_stride | p->knew_head_stride | p->vnew_batch_stride | p->vnew_row_stride | p->vnew_head_stride) & 7) ||
+                     ((((uintptr_t)p->k_new) | ((uintptr_t)p->v_new)) & 15)))
+        return fail(VATTN_K_ERR_UNSUPPORTED, "k_new / v_new must be 16-byte aligned (strides of 8 elements)");
+    if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
+    return VATTN_K_OK;
+}
+
 }  // namespace vattn_k
 
 using namespace vattn_k;
@@ -373,14 +400,7 @@ int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_sca
     if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the fp8 rule)
     int rc = validate(p);
     if (rc) return rc;
-    if (!k_scale || !v_scale) return fail(VATTN_K_ERR_INVALID, "an fp8 KV cache needs k_scale and v_scale (device float32[h_k])");
-    const int64_t strides[] = {p->k_batch_stride, p->k_row_stride, p->k_head_stride, p->v_batch_stride, p->v_row_stride, p->v_head_stride};
-    for (int64_t s : strides)
-        if (s % 16 != 0) return fail(VATTN_K_ERR_UNSUPPORTED, "fp8 cache strides must be multiples of 16 elements (16-byte vector access)");
-    if (p->k_new && (((p->knew_batch_stride | p->knew_row_stride | p->knew_head_stride | p->vnew_batch_stride | p->vnew_row_stride | p->vnew_head_stride) & 7) ||
-                     ((((uintptr_t)p->k_new) | ((uintptr_t)p->v_new)) & 15)))
-        return fail(VATTN_K_ERR_UNSUPPORTED, "k_new / v_new must be 16-byte aligned (strides of 8 elements)");
-    if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
+    if ((rc = fp8kv_check_args(p, k_scale, v_scale))) return rc;
 #ifndef VATTN_LAB
     return launch_fp8kv_form(p, k_scale, v_scale, (hipStream_t)stream);
 #else
@@ -398,6 +418,43 @@ int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* 
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
     return vattn_attn_plan_describe(p, out);
+}
+
+int vattn_fp8kv_prefill_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream) {
+    if (!abi_ok(p)) return validate(p);
+    if (const char* why = fp8kv_prefill_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the fp8 rule)
+    int rc = validate(p);
+    if (rc) return rc;
+    if ((rc = fp8kv_check_args(p, k_scale, v_scale))) return rc;
+#ifndef VATTN_LAB
+    return launch_fp8kv_prefill_form(p, k_scale, v_scale, (hipStream_t)stream);
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
+}
+
+// The prefill call over an fp8 cache takes the 2-byte call's plan without its prefill64 branch (prefill_kernels.hip, plan_prefill): tiling 1 or 4
+size_t vattn_fp8kv_prefill_workspace_bytes(const vattn_attn_params* p) {
+    if (!abi_ok(p) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || fp8kv_prefill_gate_reason(p)) return 0;
+#ifndef VATTN_LAB
+    return fp8kv_prefill_workspace_bytes(p);
+#else
+    return 0;
+#endif
+}
+
+int vattn_fp8kv_prefill_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
+    if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
+    if (const char* why = fp8kv_prefill_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    if (!out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0) return fail(VATTN_K_ERR_INVALID, "vattn_fp8kv_prefill_plan_describe: bad shape");
+#ifndef VATTN_LAB
+    memset(out, 0, sizeof *out);
+    fp8kv_prefill_describe(p, out);
+    out->workspace_bytes = (int64_t)fp8kv_prefill_workspace_bytes(p);
+    return VATTN_K_OK;
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
 }
 
 int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {

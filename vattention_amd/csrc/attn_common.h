@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/vattn_kernels.h"
 
@@ -119,6 +120,27 @@ template <typename P> __device__ __forceinline__ const P* uniform_ptr(const P* p
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
     return (const P*)(((unsigned long long)hi << 32) | lo);
+}
+
+// ---- FP8 (e4m3) KV cache: pieces shared by the builds that read one (decode_body.h, prefill_body.h: FP8) ----
+// one fp32 scale per kv head, value = stored * scale; the pointers are a kernel argument of those builds alone (vattn_attn_params is frozen)
+struct fp8_scales { const float* k; const float* v; };
+// 16 e4m3 bytes -> 16 values of T: lo = bytes 0-7, hi = bytes 8-15 (v_cvt_scalef32_pk_{f16,bf16}_fp8 with scale 1: two values per instruction)
+template <typename T> __device__ __forceinline__ void fp8_widen16(const uint4 x, uint4& lo, uint4& hi) {
+    const unsigned w[4] = {x.x, x.y, x.z, x.w};
+    unsigned r[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if constexpr (std::is_same_v<T, _Float16>) {
+            r[2 * i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, false));
+            r[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, true));
+        } else {
+            r[2 * i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, false));
+            r[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, true));
+        }
+    }
+    lo = make_uint4(r[0], r[1], r[2], r[3]);
+    hi = make_uint4(r[4], r[5], r[6], r[7]);
 }
 
 // ---- rotary position embedding, NeoX pairing (element i with element i + rot_dim/2), on 8-element fragments ----
@@ -275,6 +297,10 @@ void launch_append_fp8(const vattn_attn_params* p, const float* k_scale, const f
 dim3 prefill_grid(const vattn_attn_params* p, int nqb, int nsplit, int* order_out);      // prefill_kernels.hip: grid and workgroup order of nqb query blocks in nsplit key-range shares
 int launch_prefill_form(const vattn_attn_params* p, hipStream_t st);    // prefill_kernels.hip (seqlen_q > 1)
 size_t prefill_workspace_bytes(const vattn_attn_params* p);
+// prefill_kernels.hip (product library only): the prefill form over an e4m3 cache — the 2-byte call's plan without its prefill64 branch
+int launch_fp8kv_prefill_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st);
+size_t fp8kv_prefill_workspace_bytes(const vattn_attn_params* p);
+void fp8kv_prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out);
 int prefill_worklist(const vattn_attn_params* p, const int32_t* q_lens, const int32_t* k_lens, vattn_prefill_item* items, int cap_items,
                      vattn_prefill_item* blocks, int cap_blocks, int32_t* counts, int32_t* wg_first = nullptr, int max_wg = 0, int persist_mode = 0);   // prefill_kernels.hip; persist_mode 0 none, 1 host-assigned queues, 2 drawn queues
 void launch_prefill64p(const vattn_attn_params* p, hipStream_t st, int* ctr);      // prefill64p_kernels.hip: persistent workgroups over a work list (ctr: drawn queues)

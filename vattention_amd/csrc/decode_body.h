@@ -52,25 +52,7 @@ constexpr int DC_BN = 32;     // keys per wave tile
 // layout, which the transposed reads and the PV MFMAs see unchanged.  No fused append, no fused rotation (the host quantises k_new / v_new
 // first: launch_append_fp8).  The scale pointers are a kernel argument of these builds alone, in the place of the TREE builds' mask.
 struct no_tree_mask {};
-struct fp8_scales { const float* k; const float* v; };
 template <bool TREE, bool FP8 = false> using tree_mask_arg = std::conditional_t<TREE, const uint32_t*, std::conditional_t<FP8, fp8_scales, no_tree_mask>>;
-// 16 e4m3 bytes -> 16 values of T: lo = bytes 0-7, hi = bytes 8-15 (v_cvt_scalef32_pk_{f16,bf16}_fp8 with scale 1: two values per instruction)
-template <typename T> __device__ __forceinline__ void fp8_widen16(const uint4 x, uint4& lo, uint4& hi) {
-    const unsigned w[4] = {x.x, x.y, x.z, x.w};
-    unsigned r[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        if constexpr (std::is_same_v<T, _Float16>) {
-            r[2 * i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, false));
-            r[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, true));
-        } else {
-            r[2 * i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, false));
-            r[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, true));
-        }
-    }
-    lo = make_uint4(r[0], r[1], r[2], r[3]);
-    hi = make_uint4(r[4], r[5], r[6], r[7]);
-}
 template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,

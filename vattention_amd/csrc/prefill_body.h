@@ -18,8 +18,15 @@ namespace vattn_k {
 // keys [i + off - left, i + off]: the workgroup's key walk starts at the 64-key tile that holds the first key its FIRST row sees (tiles below
 // it are never loaded: no-read contract, T = 64) and ends where it ends without a window; key-range shares divide that walk.  The left edge is
 // masked where the causal diagonal is: wave-uniform tile classes (wave_dead: wholly left of the wave's first row; need_mask: straddles some row's limit).
-template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM, bool WIN = false>
-__device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const int b, const int h, const int qb, const int split, const int nsplit, char* smem) {
+// FP8: the K / V cache holds OCP e4m3 bytes with one fp32 scale per kv head (vattn_fp8kv_prefill_with_kvcache, include/vattn_kernels.h) — builds of
+// their own (prefill_fp8_kernel below), the others carry no trace of it.  A cache row is HD bytes, so a 16-byte load is 16 consecutive d of one key:
+// half the loads per tile, each widened in registers (exact) into the TWO 16-byte chunks of T the 2-byte build would have stored — the LDS image is
+// that build's for the unscaled values, and everything that reads LDS is unchanged.  The scales never touch an element: k_scale[hk] folds into sc
+// (and the LSE), v_scale[hk] into the final 1 / l, so partials are published scaled and combine_rows_kernel does not know the cache dtype.
+template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM, bool WIN = false, bool FP8 = false>
+__device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const int b, const int h, const int qb, const int split, const int nsplit, char* smem,
+                                             const fp8_scales scales = {}) {
+    static_assert(!FP8 || (!WIN && !MSUM && QC == 1 && USE_TR), "the fp8 cache builds: 32-row waves, no window");
     using X = Tr<T>;
     using V8 = typename X::v8;
     using S = PfSmem<HD>;
@@ -28,9 +35,12 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
     constexpr int KK = HD / 16;        // k-steps of the S^T MFMA chain
     constexpr int DB = HD / 32;        // 32-wide d blocks of O^T
     constexpr int CPR = HD / 8;        // 16-byte chunks per K/V row
-    constexpr int PASSES = (PF_BN * CPR) / NT;
+    constexpr int LCPR = FP8 ? HD / 16 : CPR;   // 16-byte chunks per LOADED row (FP8: a row is HD bytes, a loaded chunk becomes chunks 2c, 2c + 1 of T)
+    // FP8, d = 64 on 8 waves: 256 chunks for 512 threads — waves 0-3 load and store the tile, waves 4-7 skip both (wave-uniform)
+    constexpr bool HALF_WG = FP8 && PF_BN * LCPR < NT;
+    constexpr int PASSES = HALF_WG ? 1 : (PF_BN * LCPR) / NT;
     constexpr int SWZ = CPR < 16 ? CPR - 1 : 15;   // K-tile swizzle mask
-    static_assert(PASSES >= 1 && (PF_BN * CPR) % NT == 0, "tile does not divide over the workgroup");
+    static_assert(PASSES >= 1 && (HALF_WG ? NT % (PF_BN * LCPR) == 0 : (PF_BN * LCPR) % NT == 0), "tile does not divide over the workgroup");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -65,8 +75,9 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
         nt = min(nt_all, tb + per);
     }
 
-    const T* kbase = (const T*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)hk * p.k_head_stride;
-    const T* vbase = (const T*)p.v_cache + (int64_t)slot * p.v_batch_stride + (int64_t)hk * p.v_head_stride;
+    using KVT = std::conditional_t<FP8, uint8_t, T>;     // a cache element
+    const KVT* kbase = (const KVT*)p.k_cache + (int64_t)slot * p.k_batch_stride + (int64_t)hk * p.k_head_stride;
+    const KVT* vbase = (const KVT*)p.v_cache + (int64_t)slot * p.v_batch_stride + (int64_t)hk * p.v_head_stride;
 
     // ---- Q^T fragments (B operand of S^T = K.Q^T): slot (g, j) <-> d = 16*kk + 8*g + j ----
     V8 qf[QC][KK];
@@ -116,29 +127,33 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
         l_run[qc] = 0.f;
         lacc[qc] = (f32x16){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     }
-    const float sc = p.softmax_scale * kLog2e;
+    float sm_scale = p.softmax_scale;                    // FP8: k_scale[hk] folded in (scores = q . stored * k_scale)
+    if constexpr (FP8) sm_scale *= scales.k[hk];
+    const float sc = sm_scale * kLog2e;
 
     // two register sets: the loads of tile t+2 are issued while tile t is computed and are only consumed (stored to
     // LDS) at the end of iteration t+1 -> a two-iteration latency budget instead of one (L2/MALL latency under load
     // is about one tile time)
     uint4 kregA[PASSES], vregA[PASSES], kregB[PASSES], vregB[PASSES];
-    const unsigned k_rs_bytes = (unsigned)p.k_row_stride * 2u, v_rs_bytes = (unsigned)p.v_row_stride * 2u;
+    const unsigned k_rs_bytes = (unsigned)p.k_row_stride * (unsigned)sizeof(KVT), v_rs_bytes = (unsigned)p.v_row_stride * (unsigned)sizeof(KVT);
+    const bool stager = !HALF_WG || wave < (PF_BN * LCPR) / 64;      // (wave-uniform; always true but for the half-workgroup build)
     // per-thread byte offsets inside a tile (row-major rows of the cache, 16-byte chunk c)
     unsigned koff[PASSES], voff[PASSES];
 #pragma unroll
     for (int ps = 0; ps < PASSES; ps++) {
         const int idx = ps * NT + tid;
-        koff[ps] = (unsigned)(idx / CPR) * k_rs_bytes + (unsigned)(idx % CPR) * 16u;
-        voff[ps] = (unsigned)(idx / CPR) * v_rs_bytes + (unsigned)(idx % CPR) * 16u;
+        koff[ps] = (unsigned)(idx / LCPR) * k_rs_bytes + (unsigned)(idx % LCPR) * 16u;
+        voff[ps] = (unsigned)(idx / LCPR) * v_rs_bytes + (unsigned)(idx % LCPR) * 16u;
     }
-    const T* kbase_u = uniform_ptr(kbase);
-    const T* vbase_u = uniform_ptr(vbase);
+    const KVT* kbase_u = uniform_ptr(kbase);
+    const KVT* vbase_u = uniform_ptr(vbase);
     auto stage_load = [&](int t, uint4 (&kreg)[PASSES], uint4 (&vreg)[PASSES]) {
         // descriptor rebased per tile: rows at or beyond Lk fall outside num_records -> zeros, no access
         int rem = Lk - t * PF_BN;
         rem = rem < 0 ? 0 : (rem > PF_BN ? PF_BN : rem);
         const __amdgpu_buffer_rsrc_t kr = make_rsrc(kbase_u + (int64_t)t * PF_BN * p.k_row_stride, (unsigned)rem * k_rs_bytes);
         const __amdgpu_buffer_rsrc_t vr = make_rsrc(vbase_u + (int64_t)t * PF_BN * p.v_row_stride, (unsigned)rem * v_rs_bytes);
+        if (HALF_WG && !stager) return;
 #pragma unroll
         for (int ps = 0; ps < PASSES; ps++) {
             kreg[ps] = buf_load16(kr, koff[ps]);
@@ -148,6 +163,24 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
     auto stage_write = [&](int buf, const uint4 (&kreg)[PASSES], const uint4 (&vreg)[PASSES]) {
         char* ksm = smem + buf * S::kBufBytes;
         char* vsm = ksm + S::kTileBytes;
+        if constexpr (FP8) {
+            if (HALF_WG && !stager) return;
+#pragma unroll
+            for (int ps = 0; ps < PASSES; ps++) {
+                const int idx = ps * NT + tid;      // (< PF_BN * LCPR: a stager's index)
+                const int row = idx / LCPR;
+                const int c = idx % LCPR;           // 16 d of the row = chunks 2c, 2c + 1 of the 2-byte layout
+                uint4 lo, hi;
+                fp8_widen16<T>(kreg[ps], lo, hi);
+                *(uint4*)(ksm + row * S::kRowBytes + (((2 * c) ^ (row & SWZ)) << 4)) = lo;
+                *(uint4*)(ksm + row * S::kRowBytes + (((2 * c + 1) ^ (row & SWZ)) << 4)) = hi;
+                fp8_widen16<T>(vreg[ps], lo, hi);
+                char* vrow = vsm + (c >> 1) * S::kVSubBytes + row * 64 + ((c & 1) << 5);      // sub-tile (2c) >> 2, 32 contiguous bytes of its 64-byte row
+                *(uint4*)vrow = lo;
+                *(uint4*)(vrow + 16) = hi;
+            }
+            return;
+        }
 #pragma unroll
         for (int ps = 0; ps < PASSES; ps++) {
             const int idx = ps * NT + tid;
@@ -318,7 +351,8 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
     for (int qc = 0; qc < QC; qc++) {
         const int my_q = qw0 + 32 * qc + l31;
         const float l_tot = MSUM ? lacc[qc][0] : (l_run[qc] + swap_halves(l_run[qc]));
-        const float inv = (l_tot == 0.f || l_tot != l_tot) ? 1.f : 1.f / l_tot;
+        float inv = (l_tot == 0.f || l_tot != l_tot) ? 1.f : 1.f / l_tot;
+        if constexpr (FP8) inv *= scales.v[hk];      // (partials are published scaled: the merge does not know the cache dtype)
         if (my_q < Sq && nsplit > 1) {
             // KV-split: normalised fp32 partial + its log2-domain LSE; combine_kernel merges the nsplit partials of a row
             // workspace: float o_part[nsplit][B][Sq][H][HD]; float lse_part[nsplit][B][Sq][H]
@@ -374,7 +408,7 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
             }
             if (p.softmax_lse && g == 0) {
                 // natural-log LSE of scale*QK^T; +inf for fully masked rows (flash convention)
-                const float lse = (l_tot == 0.f) ? INFINITY : (m_run[qc] * p.softmax_scale + __logf(l_tot));
+                const float lse = (l_tot == 0.f) ? INFINITY : (m_run[qc] * sm_scale + __logf(l_tot));
                 p.softmax_lse[((int64_t)b * p.h + h) * p.seqlen_q + my_q] = lse;
             }
         }
@@ -387,6 +421,15 @@ __global__ __launch_bounds__(64 * WAVES, (QC == 2 || HD > 128) ? 1 : 2) void pre
     int b, h, qb, split;
     if (!wg_to_work(p, order, nqb, nsplit, b, h, qb, split)) return;
     prefill_body<T, HD, USE_TR, WAVES, QC, MSUM, WIN>(p, b, h, qb, split, nsplit, smem);      // (key-range shares are merged by combine_rows_kernel)
+}
+
+// The FP8 builds' kernel: prefill_kernel's mapping, the scale pointers as the extra argument (32-row waves, no window; launch bounds of the 2-byte sibling)
+template <typename T, int HD, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 2) void prefill_fp8_kernel(vattn_attn_params p, int order, int nqb, int nsplit, fp8_scales scales) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int b, h, qb, split;
+    if (!wg_to_work(p, order, nqb, nsplit, b, h, qb, split)) return;
+    prefill_body<T, HD, true, WAVES, 1, false, false, true>(p, b, h, qb, split, nsplit, smem, scales);
 }
 
 }  // namespace vattn_k

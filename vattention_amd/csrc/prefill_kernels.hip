@@ -4,6 +4,8 @@
 //                         softmax entirely in registers (a lane owns one query column), K tile XOR-swizzled for conflict-free
 //                         ds_read_b128, V tile as [d-block][key][32 d] sub-tiles read through ds_read_b64_tr_b16;
 //                         optional KV split (fp32 partials merged by combine_rows_kernel) and batched variable-length chunks
+//   prefill_fp8_kernel  : prefill_kernel's body over an fp8 (e4m3) cache (prefill_body.h, FP8): the bytes are widened on their way into LDS,
+//                         the per-head scales fold into the softmax scale and the final 1 / l (vattn_fp8kv_prefill_with_kvcache)
 //   prefill_ilv_kernel  : the same data flow software-pipelined with a hand-written issue order (variant 12)
 // Semantics: /root/reference/pod_attn/pod_attn/flash_attn_interface.py:1146-1291, flash_api.cpp:1291-1578, mask.h:164-196
 // (bottom-right causal), softmax.h:69-157 (fp32 max/sum, exp2, P rounded to the I/O dtype before PV).
@@ -136,11 +138,14 @@ dim3 prefill_grid(const vattn_attn_params* p, int nqb, int nsplit, int* order_ou
 //          8-wave kernel, 7 = prefill64_kernel (prefill64_kernels.hip: 4 waves x 64 rows, LDS-DMA ring, in-wave software pipeline).
 //  nsplit  > 1 when the grid would leave CUs idle (tensor-parallel shards with few heads, short chunks): every work item's
 //          key range is divided over nsplit workgroups, fp32 partials go through the workspace, combine_kernel merges them.
+//  with_p64 = false: the plan of a call that has no prefill64 build (an fp8 cache: prefill64 moves its tiles by LDS-DMA and cannot widen them in
+//          flight) — the same rules with the prefill64 branch skipped, so tiling 1 or 4 and the split count those rules give; nothing tuned apart.
 struct PrefillPlan { int tiling; int nsplit; };
-PrefillPlan plan_prefill(const vattn_attn_params* p) {
+PrefillPlan plan_prefill(const vattn_attn_params* p, const bool with_p64 = true) {
     PrefillPlan pl;
     pl.tiling = (p->variant >> 1) & 7;
     pl.nsplit = 1;
+    if (!with_p64 && pl.tiling == 7) pl.tiling = 1;      // (the fp8 gate refuses the selector in front of a launch)
     const bool auto_tiling = pl.tiling == 0;
     // The product runs tilings 0/1, 4 and — d = 128 only — 7; every other selector describes as tiling 1 (validate() rejects it in front of
     // a launch).  2 (64-row waves) and 6 (hand-interleaved, software-pipelined) are lab-only kernels (tools/lab/csrc/prefill_kernels_lab.hip);
@@ -209,7 +214,7 @@ PrefillPlan plan_prefill(const vattn_attn_params* p) {
     // 8 k prompt: 256 workgroups of 4 ... 128 key tiles) is bound by its longest workgroup's key walk; two key-range shares per
     // query block on the 8-wave tiling (two rounds, heaviest first) measure 0.192 ms against 0.239 (prefill64 unsplit), 0.226 (4-wave
     // tiling unsplit) and 0.201 (prefill64, two shares).
-    if (p->d == 128 && (uniform || wg8 > 256)) {
+    if (with_p64 && p->d == 128 && (uniform || wg8 > 256)) {
         int ns7 = wg8 >= 256 ? 1 : pick(wg8, 256);
         if (uniform && wg8 >= 256) {
             // a few rounds of EQUAL workgroups (a chunk on a long prefix): if the last round is far from full (Yi-34B/TP4: 14 heads x
@@ -252,7 +257,8 @@ static void launch_combine_rows(void (*kernel)(vattn_attn_params, int, int, int6
 }
 
 // (the single-launch merge of the key-range shares — variant bits 14 / 15 — measured slower and lives in the lab copy: profiles/r02_kbench_prefill_merge.txt)
-template <typename T, int HD, int WAVES, int QC, bool WIN = false> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit) {
+// FP8: the builds over an e4m3 cache (prefill_fp8_kernel) — the same grid, order, LDS and merge; the scales are their extra argument
+template <typename T, int HD, int WAVES, int QC, bool WIN = false, bool FP8 = false> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit, const fp8_scales sc) {
     constexpr bool MSUM = false;
     constexpr int BM = 32 * QC * WAVES;
     const int nqb = (p->seqlen_q + BM - 1) / BM;
@@ -261,11 +267,13 @@ template <typename T, int HD, int WAVES, int QC, bool WIN = false> void launch_p
     const dim3 block(64 * WAVES);
     const size_t smem = PfSmem<HD>::kTotal;
     static const bool attr_once = [] {   // 64 KiB of dynamic LDS per workgroup
-        (void)hipFuncSetAttribute((const void*)prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
+        if constexpr (FP8) (void)hipFuncSetAttribute((const void*)prefill_fp8_kernel<T, HD, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
+        else (void)hipFuncSetAttribute((const void*)prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
         return true;
     }();
     (void)attr_once;
-    hipLaunchKernelGGL((prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>), grid, block, smem, st, *p, order, nqb, nsplit);
+    if constexpr (FP8) hipLaunchKernelGGL((prefill_fp8_kernel<T, HD, WAVES>), grid, block, smem, st, *p, order, nqb, nsplit, sc);
+    else hipLaunchKernelGGL((prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>), grid, block, smem, st, *p, order, nqb, nsplit);
     launch_combine_rows(combine_rows_kernel<T, HD>, p, st, nsplit);
 }
 
@@ -275,9 +283,14 @@ static bool persistent_list(const vattn_attn_params* p) {
     return p->pf_num_wg > 0 && !p->rotary_cos_sin && ((p->o_row_stride | p->o_head_stride | p->o_batch_stride) & 7) == 0;
 }
 
-template <typename T, int HD> int launch_prefill_t(const vattn_attn_params* p, hipStream_t st) {
-    if (p->k_new && p->seqlen_knew > 0) launch_append(p, st);
-    if constexpr (HD == 128) {
+// FP8 (vattn_fp8kv_prefill_with_kvcache; the caller checked its gate: no work list, no window, no prefill64): k_new / v_new are QUANTISED into
+// the cache first, the plan is the 2-byte call's without its prefill64 branch, the kernels are the FP8 builds
+template <typename T, int HD, bool FP8 = false> int launch_prefill_t(const vattn_attn_params* p, hipStream_t st, const fp8_scales sc = {}) {
+    if (p->k_new && p->seqlen_knew > 0) {
+        if constexpr (FP8) launch_append_fp8(p, sc.k, sc.v, st);
+        else launch_append(p, st);
+    }
+    if constexpr (HD == 128 && !FP8) {
         if (p->pf_items) {        // host-planned work list: prefill64 pieces longest first, then the merge of the split blocks
             if (p->num_pf_items <= 0 || (p->num_pf_blocks > 0 && (!p->pf_blocks || !p->workspace)))
                 return fail(VATTN_K_ERR_INVALID, "pf_items needs num_pf_items, and pf_blocks + a workspace when blocks are split");
@@ -296,19 +309,24 @@ template <typename T, int HD> int launch_prefill_t(const vattn_attn_params* p, h
             return launch_status();
         }
     }
-    const PrefillPlan pl = plan_prefill(p);
+    const PrefillPlan pl = plan_prefill(p, !FP8);
     if (pl.nsplit > 1 && !p->workspace) return fail(VATTN_K_ERR_INVALID, "KV-split prefill needs a workspace (vattn_attn_workspace_bytes)");
-    if constexpr (HD == 128) {
-        if (pl.tiling == 7) {
-            launch_prefill64(p, st, pl.nsplit);
-            launch_combine_rows(combine_rows_kernel<T, 128>, p, st, pl.nsplit);
-            return launch_status();
+    if constexpr (FP8) {
+        if (pl.tiling == 4) launch_prefill<T, HD, 4, 1, false, true>(p, st, pl.nsplit, sc);
+        else launch_prefill<T, HD, 8, 1, false, true>(p, st, pl.nsplit, sc);
+    } else {
+        if constexpr (HD == 128) {
+            if (pl.tiling == 7) {
+                launch_prefill64(p, st, pl.nsplit);
+                launch_combine_rows(combine_rows_kernel<T, 128>, p, st, pl.nsplit);
+                return launch_status();
+            }
         }
+        // (a block that carries a sliding window takes the WIN builds, a window-less one the kernels it always ran)
+        const bool win = p->window_left_plus1 > 0;
+        if (pl.tiling == 4) (win ? launch_prefill<T, HD, 4, 1, true> : launch_prefill<T, HD, 4, 1>)(p, st, pl.nsplit, {});
+        else (win ? launch_prefill<T, HD, 8, 1, true> : launch_prefill<T, HD, 8, 1>)(p, st, pl.nsplit, {});
     }
-    // (a block that carries a sliding window takes the WIN builds, a window-less one the kernels it always ran)
-    const bool win = p->window_left_plus1 > 0;
-    if (pl.tiling == 4) (win ? launch_prefill<T, HD, 4, 1, true> : launch_prefill<T, HD, 4, 1>)(p, st, pl.nsplit);
-    else (win ? launch_prefill<T, HD, 8, 1, true> : launch_prefill<T, HD, 8, 1>)(p, st, pl.nsplit);
     return launch_status();
 }
 
@@ -584,16 +602,26 @@ int launch_prefill_form(const vattn_attn_params* p, hipStream_t st) {
     return f16 ? launch_prefill_t<_Float16, 128>(p, st) : launch_prefill_t<__bf16, 128>(p, st);
 }
 
-void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
+#ifndef VATTN_LAB
+int launch_fp8kv_prefill_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st) {
+    const bool f16 = p->dtype == VATTN_DTYPE_F16;
+    const fp8_scales sc{k_scale, v_scale};
+    if (p->d == 64) return f16 ? launch_prefill_t<_Float16, 64, true>(p, st, sc) : launch_prefill_t<__bf16, 64, true>(p, st, sc);
+    return f16 ? launch_prefill_t<_Float16, 128, true>(p, st, sc) : launch_prefill_t<__bf16, 128, true>(p, st, sc);
+}
+#endif
+
+// with_p64 = false: of the call over an fp8 cache (plan_prefill; its gate has refused a work list)
+static void describe_prefill(const vattn_attn_params* p, vattn_plan_desc* out, const bool with_p64) {
     out->form = 0;
-    if (p->pf_items && p->d == 128) {
+    if (with_p64 && p->pf_items && p->d == 128) {
         out->path = 1;
         out->tiling = 7;
         out->workgroups = persistent_list(p) ? p->pf_num_wg : p->num_pf_items;
         out->merge_launch = p->num_pf_blocks > 0;
         return;
     }
-    const PrefillPlan pl = plan_prefill(p);
+    const PrefillPlan pl = plan_prefill(p, with_p64);
     out->tiling = pl.tiling == 0 ? 1 : pl.tiling;
     out->nsplit = pl.nsplit;
     const int bm = pl.tiling == 7 ? 256 : pl.tiling == 4 ? 128 : 256;
@@ -601,10 +629,16 @@ void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     out->merge_launch = pl.nsplit > 1;
 }
 
-size_t prefill_workspace_bytes(const vattn_attn_params* p) {
-    if (p->pf_items) return (size_t)(p->pf_part_rows > 0 ? p->pf_part_rows : 0) * (p->d + 1) * sizeof(float);
-    const int ns = plan_prefill(p).nsplit;
+void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out) { describe_prefill(p, out, true); }
+void fp8kv_prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out) { describe_prefill(p, out, false); }
+
+static size_t split_workspace_bytes(const vattn_attn_params* p, const int ns) {
     return ns > 1 ? (size_t)ns * p->b * p->seqlen_q * p->h * (p->d + 1) * sizeof(float) : 0;
 }
+size_t prefill_workspace_bytes(const vattn_attn_params* p) {
+    if (p->pf_items) return (size_t)(p->pf_part_rows > 0 ? p->pf_part_rows : 0) * (p->d + 1) * sizeof(float);
+    return split_workspace_bytes(p, plan_prefill(p).nsplit);
+}
+size_t fp8kv_prefill_workspace_bytes(const vattn_attn_params* p) { return split_workspace_bytes(p, plan_prefill(p, false).nsplit); }
 
 }  // namespace vattn_k

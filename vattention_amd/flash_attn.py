@@ -180,13 +180,14 @@ def relaunch(p, q_ptr: int, k_new_ptr: int, v_new_ptr: int, out_ptr: int, k_cach
     _issue(p, dev, *fast)
 
 
-def _issue(p, dev, lib, need=None, mask=None, scales=None):
+def _issue(p, dev, lib, need=None, mask=None, scales=None, fp8_prefill=False):
     """The one launch: the workspace the call needs (asked of the library unless `need` is known: relaunch) from the per-(device, stream)
     cache, the call on the current stream — the tree-masked entry point iff `mask` is given, the fp8-cache entry point iff `scales` =
-    (k_scale, v_scale; either may be None: the library refuses that) — and its return code as an exception (the -10 of those two entries
-    names the rule of their gate that the block breaks: NotImplementedError).  Returns the workspace need."""
+    (k_scale, v_scale; either may be None: the library refuses that; fp8_prefill: its prefill-form sibling) — and its return code as an
+    exception (the -10 of those entries names the rule of their gate that the block breaks: NotImplementedError).  Returns the workspace need."""
     if need is None:
-        need = (lib.vattn_tree_attn_workspace_bytes if mask is not None else lib.vattn_fp8kv_attn_workspace_bytes if scales is not None
+        need = (lib.vattn_tree_attn_workspace_bytes if mask is not None else
+                (lib.vattn_fp8kv_prefill_workspace_bytes if fp8_prefill else lib.vattn_fp8kv_attn_workspace_bytes) if scales is not None
                 else lib.vattn_attn_workspace_bytes)(C.byref(p))
     st = K.current_stream_ptr(dev)
     if need:
@@ -194,7 +195,8 @@ def _issue(p, dev, lib, need=None, mask=None, scales=None):
     if mask is not None:
         rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
     elif scales is not None:
-        rc = lib.vattn_fp8kv_attn_with_kvcache(C.byref(p), *(s.data_ptr() if s is not None else None for s in scales), st)
+        rc = (lib.vattn_fp8kv_prefill_with_kvcache if fp8_prefill else lib.vattn_fp8kv_attn_with_kvcache)(
+            C.byref(p), *(s.data_ptr() if s is not None else None for s in scales), st)
     else:
         rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
     if rc != 0:
@@ -434,14 +436,40 @@ def flash_attn_fp8kv_with_kvcache(q, k_cache, v_cache, k_scale, v_scale, k=None,
     8 query rows, or seqlen_q * Hq / Hkv > 64) raises NotImplementedError with the library's message, which names the rule.  `_num_splits` < 0: the decode kernels' forced grids, `_variant`: the product's A/B selectors (tests, tools/kbench.py)."""
     p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse,
                                                               cache_dtype=torch.float8_e4m3fn)
-    for s in (k_scale, v_scale):
-        if s is not None and (not s.is_cuda or s.dtype != torch.float32 or s.shape != (p.h_k,) or not s.is_contiguous()):
-            raise RuntimeError("k_scale / v_scale must be contiguous float32 [num_kv_heads] GPU tensors")
+    _check_scales(k_scale, v_scale, p.h_k)
     p.is_causal = 1 if causal else 0
     _set_scalars(p, keep[0], _num_splits, softmax_scale)
     p.variant = int(_variant)
     _issue(p, dev, K.klib(), None, None, (k_scale, v_scale))      # (the product library only; a block outside the gate is refused by the call)
     counters["fp8kv_decode_calls"] += 1
+    return (out, lse) if return_softmax_lse else out
+
+
+def _check_scales(k_scale, v_scale, Hkv):
+    for s in (k_scale, v_scale):      # (None reaches the library, which refuses it)
+        if s is not None and (not s.is_cuda or s.dtype != torch.float32 or s.shape != (Hkv,) or not s.is_contiguous()):
+            raise RuntimeError("k_scale / v_scale must be contiguous float32 [num_kv_heads] GPU tensors")
+
+
+def flash_attn_fp8kv_prefill_with_kvcache(q, k_cache, v_cache, k_scale, v_scale, k=None, v=None, cache_seqlens: Optional[Union[int, torch.Tensor]] = None,
+                                          cache_batch_idx: Optional[torch.Tensor] = None, softmax_scale=None, causal=False, return_softmax_lse=False,
+                                          out=None, _num_splits: int = 0, _variant: int = 0):
+    """MI355X extension (include/vattn_kernels.h, "Prefill over an fp8 cache"): the prefill form — every q [B, Sq, Hq, D] that
+    flash_attn_fp8kv_with_kvcache refuses as such — over a float8_e4m3fn cache; arguments as there.  `k` / `v` are quantised and appended at
+    cache_seqlens FIRST, so a chunk attends to its own keys as stored (what decode reads later).  The plan is the 2-byte call's without
+    prefill64 (tiling 1 or 4); no window, no fused rotary, no host-side plan or work list on this path.  A call outside the gate (a decode-form
+    block, explicit tiling 7) raises NotImplementedError with the library's message.  `_num_splits` > 0: that many key-range shares,
+    `_variant`: explicit tiling 1 / 4 and the workgroup order (tests, tools/kbench.py)."""
+    p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse,
+                                                              cache_dtype=torch.float8_e4m3fn)
+    _check_scales(k_scale, v_scale, p.h_k)
+    hint = cache_seqlens + Sn if isinstance(cache_seqlens, int) else 0      # (a host-side bound on the lengths sizes the key-range split)
+    p.max_seqlen_k_hint = min(hint, Sk + Sn) if hint > 0 else 0
+    p.is_causal = 1 if causal else 0
+    _set_scalars(p, keep[0], _num_splits, softmax_scale)
+    p.variant = int(_variant)
+    _issue(p, dev, K.klib(), None, None, (k_scale, v_scale), True)
+    counters["fp8kv_prefill_calls"] += 1
     return (out, lse) if return_softmax_lse else out
 
 
@@ -466,7 +494,7 @@ _plan_cache = {}      # (shapes, lengths, device, stream) -> _PrefillPlan; a few
 # with other lengths in between gets plans sized for the wrong lengths; False switches the lookup off (the view's row count then bounds
 # the plan, FlashAttention's own rule).
 USE_PAGE_MANAGER_LENGTHS = True
-counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "fp8kv_decode_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
+counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "fp8kv_decode_calls": 0, "fp8kv_prefill_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
 
 
 def _cached_prefill_plan(p, klens, dev):
@@ -640,12 +668,32 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q
     already be in the cache (cache_flat).  Bottom-right-aligned causal mask per entry, exactly as flash_attn_with_kvcache
     does for one sequence (the reference's wrapper issues one call per prompt, vattention_flashattention_wrapper.py:129-174).
     `window_size=(left, right)`: causal sliding window per entry, rules as flash_attn_with_kvcache."""
+    p, keep, out, dev = _build_varlen_block(q, k_cache, v_cache, q_start, q_lens, max_q_len, cache_seqlens, cache_batch_idx, out)
+    T, Hq, D = q.shape
+    Sk = k_cache.shape[1]
+    p.window_left_plus1, causal = _window_left_plus1(window_size, bool(causal), int(max_q_len), Sk)
+    p.is_causal = 1 if causal else 0
+    _set_scalars(p, q, num_splits, softmax_scale)
+    p.variant = int(_variant)
+    p.max_seqlen_k_hint = min(int(_max_seqlen_k), Sk) if _max_seqlen_k > 0 else 0
+    if _rotary_cos_sin is not None:      # q rows of entry i are rotated at positions (cache_seqlens[i] - q_lens[i]) + row
+        rot = _rotary_table(None, None, _rotary_cos_sin, False, q)
+        p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
+    if isinstance(_pf_plan, _PrefillPlan) and D == 128 and num_splits == 0 and not _capture_active() and not p.window_left_plus1:
+        _pf_plan.attach(p)        # work list built from the host-side lengths of this iteration (prefill_plan)
+    _launch(p, dev, keep=keep + (_rotary_cos_sin, _pf_plan))
+    return out
+
+
+def _build_varlen_block(q, k_cache, v_cache, q_start, q_lens, max_q_len, cache_seqlens, cache_batch_idx, out, cache_dtype=None):
+    """The shared front half of the batched-chunk entry points (q / out [T, Hq, D]): argument checks, `out`, and an AttnParams with its tensor,
+    stride, index and shape fields filled.  Returns (block, the tensors it points to — to be kept alive —, out, device)."""
     _check_cuda(q, k_cache, v_cache, q_start, q_lens, cache_seqlens, cache_batch_idx)
     if q.dim() != 3:
         raise RuntimeError("q must be [total_tokens, num_heads, head_size]")
     T, Hq, D = q.shape
     Bc, Sk, Hkv, Dk = k_cache.shape
-    _check_dtypes(q, k_cache, v_cache)
+    _check_dtypes(q, k_cache, v_cache, cache_dtype)
     q_start, q_lens, cache_seqlens = _index_tensor(q_start, "q_start"), _index_tensor(q_lens, "q_lens"), _index_tensor(cache_seqlens, "seqlens_k")
     B = q_lens.shape[0]
     assert q_start.shape == (B,) and cache_seqlens.shape == (B,)
@@ -658,22 +706,28 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q
         raise RuntimeError("max_q_len must be >= 2 (single-token queries take the decode form)")
     assert k_cache.stride(-1) == 1 and v_cache.stride(-1) == 1 and q.stride(-1) == 1
     out = _check_out(out, q)
-    dev = q.device
     p = K.AttnParams()
     _set_q_out(p, q, out)
     _set_cache(p, k_cache, v_cache)
     p.cache_seqlens, p.q_start, p.q_lens = cache_seqlens.data_ptr(), q_start.data_ptr(), q_lens.data_ptr()
     p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
     p.b, p.seqlen_q, p.seqlen_k, p.seqlen_knew, p.h, p.h_k, p.d = B, int(max_q_len), Sk, 0, Hq, Hkv, D
-    p.window_left_plus1, causal = _window_left_plus1(window_size, bool(causal), int(max_q_len), Sk)
+    return p, (q, k_cache, v_cache, q_start, q_lens, cache_seqlens, cache_batch_idx, out), out, q.device
+
+
+def flash_attn_fp8kv_varlen_with_kvcache(q, k_cache, v_cache, k_scale, v_scale, q_start: torch.Tensor, q_lens: torch.Tensor, max_q_len: int,
+                                         cache_seqlens: torch.Tensor, cache_batch_idx: Optional[torch.Tensor] = None, softmax_scale=None,
+                                         causal=True, out=None, _num_splits: int = 0, _variant: int = 0, _max_seqlen_k: int = 0):
+    """flash_attn_varlen_with_kvcache over a float8_e4m3fn cache (include/vattn_kernels.h, "Prefill over an fp8 cache"): ONE launch for the
+    prefill chunks of several sequences; q / out [T, Hq, D] fp16 / bf16, k_scale / v_scale float32 [Hkv] GPU tensors.  The chunks' own K/V
+    must already be in the cache (cache_ops.cache_flat_fp8).  No window, no fused rotary and no work list on this path."""
+    p, keep, out, dev = _build_varlen_block(q, k_cache, v_cache, q_start, q_lens, max_q_len, cache_seqlens, cache_batch_idx, out,
+                                            cache_dtype=torch.float8_e4m3fn)
+    _check_scales(k_scale, v_scale, p.h_k)
     p.is_causal = 1 if causal else 0
-    _set_scalars(p, q, num_splits, softmax_scale)
+    _set_scalars(p, q, _num_splits, softmax_scale)
     p.variant = int(_variant)
-    p.max_seqlen_k_hint = min(int(_max_seqlen_k), Sk) if _max_seqlen_k > 0 else 0
-    if _rotary_cos_sin is not None:      # q rows of entry i are rotated at positions (cache_seqlens[i] - q_lens[i]) + row
-        rot = _rotary_table(None, None, _rotary_cos_sin, False, q)
-        p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
-    if isinstance(_pf_plan, _PrefillPlan) and D == 128 and num_splits == 0 and not _capture_active() and not p.window_left_plus1:
-        _pf_plan.attach(p)        # work list built from the host-side lengths of this iteration (prefill_plan)
-    _launch(p, dev, keep=(q, k_cache, v_cache, q_start, q_lens, cache_seqlens, cache_batch_idx, out, _rotary_cos_sin, _pf_plan))
+    p.max_seqlen_k_hint = min(int(_max_seqlen_k), p.seqlen_k) if _max_seqlen_k > 0 else 0
+    _issue(p, dev, K.klib(), None, None, (k_scale, v_scale), True)
+    counters["fp8kv_prefill_calls"] += 1
     return out
