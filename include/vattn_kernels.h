@@ -251,7 +251,8 @@ int vattn_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* o
  * place and race-free: a thread owns one 16-byte chunk column, reads that chunk of all kept rows into registers, then stores them.  No
  * other byte of the cache is written; rows at or past row0 + keep_cnt keep their contents.  The caller guarantees that rows
  * [row0, row0 + n_draft) lie inside the cache view.  All index arrays are DEVICE int32.  Limits: n_draft <= 8, 2-byte dtypes
- * (VATTN_DTYPE_*), d 64 / 128, strides multiples of 8 elements — anything else is VATTN_K_ERR_UNSUPPORTED. */
+ * (VATTN_DTYPE_*; an fp8 cache: vattn_cache_keep_rows_fp8 below), d 64 / 128, strides multiples of 8 elements — anything else is
+ * VATTN_K_ERR_UNSUPPORTED. */
 int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
                           int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride,
                           const int32_t* row0,            /* device int32[b]: first draft row of each entry */
@@ -259,6 +260,20 @@ int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, 
                           const int32_t* keep_idx,        /* device int32[b * n_draft], strictly ascending per entry */
                           const int32_t* keep_cnt,        /* device int32[b], 0..n_draft */
                           int32_t b, int32_t n_draft, int32_t h_k, int32_t d, int32_t dtype, void* stream);
+
+/* vattn_cache_keep_rows over an fp8 (e4m3) cache — the compaction behind vattn_fp8kv_tree_attn_with_kvcache below.  The arguments of
+ * vattn_cache_keep_rows without `dtype`: elements are single bytes, strides are in bytes.  The same contract: in place and race-free (a thread
+ * owns one 16-byte chunk column — 16 elements — and reads that chunk of all kept rows before it stores them), no other byte of the cache is
+ * written, rows at or past row0 + keep_cnt keep their contents, bytes are moved as they are (no scale is read: a row keeps its kv heads'
+ * scales).  Limits: n_draft <= 8, d 64 / 128 (4 / 8 chunks per row and head), row / head / batch strides multiples of 16, 16-byte aligned
+ * bases — anything else is VATTN_K_ERR_UNSUPPORTED. */
+int vattn_cache_keep_rows_fp8(void* k_cache, void* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
+                              int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride,
+                              const int32_t* row0,            /* device int32[b]: first draft row of each entry */
+                              const int32_t* cache_batch_idx, /* or NULL */
+                              const int32_t* keep_idx,        /* device int32[b * n_draft], strictly ascending per entry */
+                              const int32_t* keep_cnt,        /* device int32[b], 0..n_draft */
+                              int32_t b, int32_t n_draft, int32_t h_k, int32_t d, void* stream);
 
 /* FP8 KV CACHE (OCP e4m3): halves the K/V bytes a decode step reads, doubles the tokens per physical page.  Additive: vattn_attn_params and
  * VATTN_KERNELS_ABI are unchanged, the scale pointers travel BESIDE the parameter block as extra arguments of builds of the decode kernels
@@ -288,8 +303,8 @@ int vattn_cache_flat_fp8(const void* key, const void* value, void* k_cache, void
  * the attention launch on the same stream (no fused in-kernel append, no fused rotary in these builds).
  * GATE: the one-token decode form (seqlen_q == 1) and the causal / non-causal multi-token form (its gate above).  Refused with
  * VATTN_K_ERR_UNSUPPORTED and a message that names the rule: window_left_plus1 > 0, rotary_cos_sin, split_items, q_lens / pf_items, the
- * prefill form, a -DVATTN_LAB build.  A tree mask and vattn_hybrid_attn have no fp8 entry point: their caches are 2-byte.  NULL scales:
- * VATTN_K_ERR_INVALID.
+ * prefill form, a -DVATTN_LAB build.  A tree mask has an entry point of its own (vattn_fp8kv_tree_attn_with_kvcache below); vattn_hybrid_attn
+ * has no fp8 entry point: its caches are 2-byte.  NULL scales: VATTN_K_ERR_INVALID.
  * PLAN: planners, grids, stream decomposition, record layouts, merge / combine kernels and workspace sizes are those of
  * vattn_flash_attn_with_kvcache for the same block — nothing is tuned apart; partials are fp32, published already scaled by v_scale, and do
  * not know the cache dtype.  vattn_fp8kv_attn_workspace_bytes / _plan_describe answer what that call gets (0 / an error outside the gate).
@@ -297,6 +312,34 @@ int vattn_cache_flat_fp8(const void* key, const void* value, void* k_cache, void
 int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream);
 size_t vattn_fp8kv_attn_workspace_bytes(const vattn_attn_params* p);
 int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
+
+/* TREE-MASKED MULTI-TOKEN FORM over an fp8 cache: verifying a draft tree against e4m3 K/V — the tree-masked form and the fp8 decode call above,
+ * multiplied: builds of the decode kernels of their own whose last argument carries the mask words AND the scale pointers; every other
+ * kernel, entry point and refusal is what it was (vattn_tree_attn_with_kvcache still takes 2-byte caches only, vattn_fp8kv_attn_with_kvcache
+ * still refuses a window).  Conventions of the fp8 decode call: p->dtype is the dtype of q / out / k_new / v_new, cache strides in bytes,
+ * device scales the host never dereferences; of the tree call: tree_mask is device uint32[b * seqlen_q], only the low seqlen_q bits of a
+ * word are read, never by the host — calls stay graph-capturable.
+ * VISIBILITY: the tree call's, on the stored values — with Lk = cache_seqlens[b] + seqlen_knew (clamped to the view) and base = Lk -
+ * seqlen_q, query token t sees every key j < base and draft key base + s iff bit s of tree_mask[b * seqlen_q + t] is set and base + s >= 0;
+ * is_causal is ignored; any bit pattern is legal; a row without a visible key gives 0 and LSE +inf.  value = stored * scale: k_scale[hk]
+ * folds into the softmax scale, v_scale[hk] into the final 1 / l and into published partials; the bytes are widened in registers (exact) and
+ * the mask is a select on the scores of the at most two tail tiles: no rounding step is added over either parent.  A chain (word t =
+ * (2 << t) - 1) equals the causal multi-token fp8 call, all ones the non-causal one, up to the order of the fp32 sums.  k_new / v_new are
+ * quantised into rows cache_seqlens[b] .. by the append launch in front of the attention launch (vattn_cache_flat_fp8's bytes).
+ * GATE: tree_mask == NULL delegates to vattn_fp8kv_attn_with_kvcache(p, k_scale, v_scale, stream), unchanged.  Otherwise the block must take
+ * the multi-token form (its gate above: 2 <= seqlen_q <= 8, seqlen_q * G <= 64, no q_lens / pf_items / split_items / rotary_cos_sin, tiling
+ * bits zero, num_splits <= 0, the product library) and carry nothing the fp8 decode gate refuses, else VATTN_K_ERR_UNSUPPORTED with a message
+ * that names the rule; window_left_plus1 > 0 beside a mask is VATTN_K_ERR_INVALID as in the 2-byte tree call; NULL scales are
+ * VATTN_K_ERR_INVALID, and the fp8 stride / alignment rules hold (cache strides multiples of 16, k_new / v_new 16-byte aligned).
+ * PLAN: planners, grids, stream decomposition, record layout, merges and workspace are those of the multi-token call on the same block —
+ * vattn_fp8kv_tree_attn_workspace_bytes / _plan_describe answer exactly what vattn_tree_attn_workspace_bytes / _plan_describe answer (0 / an
+ * error outside the gate); nothing is tuned apart.
+ * CONTRACT: no K/V load at or beyond Lk.  Draft keys a row must not see ARE loaded (they are other rows' keys) and masked before the softmax:
+ * they must hold data like any visible row, never sit on unmapped pages.  vattn_cache_keep_rows_fp8 compacts the accepted path afterwards. */
+int vattn_fp8kv_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale,
+                                       void* stream);
+size_t vattn_fp8kv_tree_attn_workspace_bytes(const vattn_attn_params* p);
+int vattn_fp8kv_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
 
 /* Prefill over an fp8 cache: chunk n of a prompt attends to chunks 0 .. n-1 as the fp8 bytes they were stored as.  Same conventions as the
  * decode call above (p->dtype, strides in bytes, device scales, stride / alignment rules).  Builds of their own of the register-staged

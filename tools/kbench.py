@@ -230,6 +230,76 @@ def fp8_ab(name, B, sq, Hq, Hkv, ctx, slots, ragged=False):
     print("    ratio 2-byte / fp8 : %.2fx" % (m16 / m8), flush=True)
 
 
+def fp8_tree_ab(B, sq, Hq, Hkv, ctx, ragged=False):
+    """multitoken --kv-fp8 --tree: ONE block (q [B, sq, Hq, 128], the sq draft rows appended at ctx - sq) through four entry points, ALTERNATING
+    in one process over the same R rotating caches (R x the 2-byte K/V bytes >= 1.5 GB), warmed up, five windows each, HIP events around each
+    window: (a) vattn_fp8kv_tree_attn_with_kvcache with a CHAIN mask, (b) vattn_fp8kv_attn_with_kvcache, causal — the same visibility: what the
+    mask costs on fp8; (c) vattn_tree_attn_with_kvcache with the chain mask over the 2-byte caches — what fp8 saves on a tree; (d) the causal
+    2-byte multi-token call.  sq = 7: also the 7-node, 3-leaf tree 0-1-{3,4}, 0-2-5-6 through both tree entries."""
+    from vattention_amd.cache_ops import cache_flat_fp8
+    torch.manual_seed(0)
+    lib, st = K.klib(), torch.cuda.current_stream().cuda_stream
+    by16 = B * 2.0 * ctx * Hkv * 128 * 2
+    R = max(2, int(1.5e9 // by16) + 1)
+    lens = [ctx - sq - (i * 7919 % (ctx - ctx // 8)) for i in range(B)] if ragged else [ctx - sq] * B
+    cl = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    idx = torch.arange(B, dtype=torch.int32, device=DEV)
+    q = torch.randn(B, sq, Hq, 128, device=DEV, dtype=DTYPE)
+    kn, vn = torch.randn(B, sq, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, sq, Hkv, 128, device=DEV, dtype=DTYPE)
+    ks = torch.full((Hkv,), 6.0 / 448.0, dtype=torch.float32, device=DEV)       # N(0,1) data: amax over 10^8 samples is below 6
+    vs = ks.clone()
+    words = lambda w: torch.tensor(w, dtype=torch.int32, device=DEV).expand(B, sq).contiguous()
+    chain = words([(2 << t) - 1 for t in range(sq)])
+    p16, p8 = [], []
+    for _ in range(R):
+        kc, vc = torch.randn(B, ctx, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, ctx, Hkv, 128, device=DEV, dtype=DTYPE)
+        k8, v8 = torch.empty(B, ctx, Hkv, 128, device=DEV, dtype=torch.float8_e4m3fn), torch.empty(B, ctx, Hkv, 128, device=DEV, dtype=torch.float8_e4m3fn)
+        cache_flat_fp8(kc.view(-1, Hkv, 128), vc.view(-1, Hkv, 128), k8.view(-1, Hkv, 128), v8.view(-1, Hkv, 128), ks, vs)
+        p16.append(params(q, kc, vc, cl, idx, kn, vn))
+        p8.append(params(q, k8, v8, cl, idx, kn, vn))          # (the workspace need is the 2-byte call's: the same planners)
+    d = K.describe_fp8kv_tree(p8[0][0])
+    assert d == K.describe_tree(p16[0][0]) == K.describe(p16[0][0]) and d["form"] == 1, d
+    ksp, vsp = ks.data_ptr(), vs.data_ptr()
+    runs = [("(a) fp8 tree entry, chain mask ", lambda pp: lib.vattn_fp8kv_tree_attn_with_kvcache(C.byref(pp), chain.data_ptr(), ksp, vsp, st), p8, 1),
+            ("(b) fp8 causal multi-token call", lambda pp: lib.vattn_fp8kv_attn_with_kvcache(C.byref(pp), ksp, vsp, st), p8, 1),
+            ("(c) 2-byte tree entry, chain   ", lambda pp: lib.vattn_tree_attn_with_kvcache(C.byref(pp), chain.data_ptr(), st), p16, 2),
+            ("(d) 2-byte causal multi-token  ", lambda pp: lib.vattn_flash_attn_with_kvcache(C.byref(pp), st), p16, 2)]
+    if sq == 7:
+        leaf3 = words([0b1, 0b11, 0b101, 0b1011, 0b10011, 0b100101, 0b1100101])
+        runs += [("(e) fp8 tree entry, 3-leaf tree", lambda pp: lib.vattn_fp8kv_tree_attn_with_kvcache(C.byref(pp), leaf3.data_ptr(), ksp, vsp, st), p8, 1),
+                 ("(f) 2-byte tree entry, 3-leaf  ", lambda pp: lib.vattn_tree_attn_with_kvcache(C.byref(pp), leaf3.data_ptr(), st), p16, 2)]
+    runs.append(("(b') the call of (b) again     ", runs[1][1], p8, 1))      # the same code twice: what two lines of this table differ by on their own
+    iters = max(2, 400 // R + 1)                                # (windows of ~0.1 s)
+
+    def window(call, ps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            for pp, _k in ps:
+                if call(pp) != 0:
+                    raise RuntimeError(K.last_error(lib))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / (iters * len(ps)) * 1e3
+    for _n, call, ps, _e in runs:                               # warm-up: every cache of every run
+        window(call, ps)
+    t = [[] for _ in runs]
+    for _rep in range(5):                                       # alternating windows
+        for i, (_n, call, ps, _e) in enumerate(runs):
+            t[i].append(window(call, ps))
+    med = [sorted(x)[2] for x in t]
+    vis = sum(n + sq for n in lens)
+    print("  B=%3d sq=%d ctx=%6d%s Hq=%2d Hkv=%d %s  path %d tiling %d wg %d, %d rotating caches" % (
+        B, sq, ctx, " ragged" if ragged else "", Hq, Hkv, "bf16" if DTYPE == torch.bfloat16 else "fp16", d["path"], d["tiling"], d["workgroups"], R))
+    for (name, _c, _p, esz), m, x in zip(runs, med, t):
+        by = vis * 2.0 * Hkv * 128 * esz + 2.0 * B * sq * Hq * 128 * 2
+        print("    %s : median %8.1f us  (5 windows: %s; spread %.1f%%)  %7.1f GB/s = %.1f%% of the 6290 GB/s read stream" % (
+            name, m, " ".join("%.1f" % y for y in x), 100.0 * (max(x) - min(x)) / m, by / m / 1e3, by / m / 1e3 / 62.9))
+    print("    ratios: (a) / (b) = %.3f [the mask on fp8]   (b') / (b) = %.3f [the same call twice]   (c) / (a) = %.2fx [fp8 on a tree]   (d) / (b) = %.2fx [fp8 on the causal call]   (c) / (d) = %.3f%s" % (
+        med[0] / med[1], med[-1] / med[1], med[2] / med[0], med[3] / med[1], med[2] / med[3],
+        "   (e) / (a) = %.3f   (f) / (e) = %.2fx" % (med[4] / med[0], med[5] / med[4]) if sq == 7 else ""), flush=True)
+
+
 def fp8_prefill_ab(name, Hq, Hkv, n, c):
     """prefill --kv-fp8: ONE block — a causal chunk of n rows whose keys [0, c + n) are in the cache — timed three ways, ALTERNATING in one
     process over R rotating caches (R x the 2-byte K/V bytes beyond the 256 MiB Infinity Cache, at most 24), warmed up, five windows each:
@@ -401,7 +471,7 @@ if __name__ == "__main__":
     if "--variants" in sys.argv:
         VARIANTS = [int(x) for x in sys.argv[sys.argv.index("--variants") + 1].split(",")]
     if "multitoken" in sys.argv:
-        # multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base build/base/libvattn_amd.so] [--bf16]
+        # multitoken --mt B,sq,Hq,Hkv,ctx[,ragged] [--mt ...] [--base build/base/libvattn_amd.so] [--bf16] [--tree] [--kv-fp8 [--tree]]
         base = sys.argv[sys.argv.index("--base") + 1] if "--base" in sys.argv else None
         TREE = "--tree" in sys.argv
         shapes = []
@@ -415,7 +485,10 @@ if __name__ == "__main__":
             sys.exit("kbench multitoken: give at least one --mt B,sq,Hq,Hkv,ctx[,ragged]")
         torch.zeros(1, device=DEV)
         for dims, ragged in shapes:
-            if "--kv-fp8" in sys.argv:
+            if "--kv-fp8" in sys.argv and TREE:          # the fp8 tree entry beside the fp8 causal call and the 2-byte tree call
+                B_, sq_, Hq_, Hkv_, ctx_ = dims
+                fp8_tree_ab(B_, sq_, Hq_, Hkv_, ctx_ + sq_, ragged)
+            elif "--kv-fp8" in sys.argv:
                 B_, sq_, Hq_, Hkv_, ctx_ = dims
                 fp8_ab("multi-token", B_, sq_, Hq_, Hkv_, ctx_ + sq_, B_, ragged)
             else:

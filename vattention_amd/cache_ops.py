@@ -106,7 +106,8 @@ def keep_rows(k_cache: torch.Tensor, v_cache: torch.Tensor, row0: torch.Tensor, 
     call (flash_attn.flash_attn_tree_with_kvcache), in place, on the current stream.  Caches [Bc, rows, Hkv, D] (any strided view with a
     contiguous last dimension); row0 int32 [B]: first draft row of each entry (the cache_seqlens of the verify call); keep_idx int32
     [B, n_draft <= 8]: the draft rows to keep, strictly ascending per entry; keep_cnt int32 [B]: how many of them.  Row row0 + i of slot
-    cache_batch_idx[b] receives row row0 + keep_idx[b, i] for i < keep_cnt[b]; nothing else is written.  No host synchronisation."""
+    cache_batch_idx[b] receives row row0 + keep_idx[b, i] for i < keep_cnt[b]; nothing else is written.  No host synchronisation.
+    float8_e4m3fn caches (behind flash_attn.flash_attn_fp8kv_tree_with_kvcache) go to vattn_cache_keep_rows_fp8: the same contract over bytes."""
     ts = (k_cache, v_cache, row0, keep_idx, keep_cnt, cache_batch_idx)
     if not all(t.is_cuda for t in ts if t is not None):
         raise RuntimeError("vattention_amd.cache_ops: tensors must live on the GPU (there is no CPU path)")
@@ -126,9 +127,12 @@ def keep_rows(k_cache: torch.Tensor, v_cache: torch.Tensor, row0: torch.Tensor, 
         return
     row0, keep_idx, keep_cnt = row0.contiguous(), keep_idx.contiguous(), keep_cnt.contiguous()
     cbi = cache_batch_idx.contiguous() if cache_batch_idx is not None else None
-    rc = K.klib().vattn_cache_keep_rows(k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
-                                        v_cache.stride(0), v_cache.stride(1), v_cache.stride(2), row0.data_ptr(),
-                                        cbi.data_ptr() if cbi is not None else None, keep_idx.data_ptr(), keep_cnt.data_ptr(), B, n_draft,
-                                        k_cache.shape[2], k_cache.shape[3], K.dtype_code(k_cache.dtype), K.current_stream_ptr(k_cache.device))
+    args = (k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+            v_cache.stride(0), v_cache.stride(1), v_cache.stride(2), row0.data_ptr(),
+            cbi.data_ptr() if cbi is not None else None, keep_idx.data_ptr(), keep_cnt.data_ptr(), B, n_draft, k_cache.shape[2], k_cache.shape[3])
+    if k_cache.dtype == torch.float8_e4m3fn:      # (elements = bytes: the strides already are byte counts)
+        rc = K.klib().vattn_cache_keep_rows_fp8(*args, K.current_stream_ptr(k_cache.device))
+    else:
+        rc = K.klib().vattn_cache_keep_rows(*args, K.dtype_code(k_cache.dtype), K.current_stream_ptr(k_cache.device))
     if rc != 0:
         raise (NotImplementedError if rc == -10 else RuntimeError)(K.last_error())

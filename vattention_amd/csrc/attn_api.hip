@@ -318,6 +318,13 @@ static const char* fp8kv_gate_reason(const vattn_attn_params* p) {
     return nullptr;
 }
 
+// ... of the tree-masked call over an fp8 cache (vattn_fp8kv_tree_attn_with_kvcache): the multi-token form's gate, rule by rule as the 2-byte tree
+// call names it, then whatever the fp8 decode gate refuses (the window is refused before either, as an INVALID argument: kTreeWindow)
+static const char* fp8kv_tree_gate_reason(const vattn_attn_params* p) {
+    if (const char* why = tree_gate_reason(p)) return why;
+    return fp8kv_gate_reason(p);
+}
+
 // ... and of the PREFILL form over an fp8 cache (vattn_fp8kv_prefill_with_kvcache): every block that decode_form() rejects, on the register-staged
 // prefill kernels (prefill_body.h, FP8) under the default launch — no window, rotation, host plan or prefill64 there
 static const char* fp8kv_prefill_gate_reason(const vattn_attn_params* p) {
@@ -417,6 +424,35 @@ size_t vattn_fp8kv_attn_workspace_bytes(const vattn_attn_params* p) {
 int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    return vattn_attn_plan_describe(p, out);
+}
+
+int vattn_fp8kv_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale, void* stream) {
+    if (!tree_mask) return vattn_fp8kv_attn_with_kvcache(p, k_scale, v_scale, stream);
+    if (!abi_ok(p)) return validate(p);
+    if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);      // (as in the 2-byte tree call; before the gates: the fp8 gate would call it unsupported)
+    if (const char* why = fp8kv_tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the rule)
+    int rc = validate(p);
+    if (rc) return rc;
+    if ((rc = fp8kv_check_args(p, k_scale, v_scale))) return rc;
+#ifndef VATTN_LAB
+    return launch_fp8kv_tree_form(p, tree_mask, k_scale, v_scale, (hipStream_t)stream);
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
+}
+
+// The tree-masked call over an fp8 cache runs the multi-token launch of the same block on other builds of the same kernels: what
+// vattn_tree_attn_workspace_bytes / _plan_describe answer.
+size_t vattn_fp8kv_tree_attn_workspace_bytes(const vattn_attn_params* p) {
+    if (!abi_ok(p) || p->window_left_plus1 > 0 || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || fp8kv_tree_gate_reason(p)) return 0;
+    return vattn_attn_workspace_bytes(p);
+}
+
+int vattn_fp8kv_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
+    if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
+    if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);
+    if (const char* why = fp8kv_tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
     return vattn_attn_plan_describe(p, out);
 }
 

@@ -313,6 +313,8 @@ int* merge_counters(hipStream_t st, size_t n_ints);                      // attn
 int launch_decode_form(const vattn_attn_params* p, hipStream_t st);     // decode_kernels.hip (decode_form(p): seqlen_q == 1, or the multi-token form)
 int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st);   // decode_kernels.hip (product library only): the tree-masked multi-token form
 int launch_fp8kv_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st);   // decode_kernels.hip (product library only): decode_form(p) over an e4m3 cache
+// decode_kernels.hip (product library only): the tree-masked multi-token form over an e4m3 cache
+int launch_fp8kv_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale, hipStream_t st);
 size_t decode_workspace_bytes(const vattn_attn_params* p);
 int decode_plan(const vattn_attn_params* p, const int32_t* lens, vattn_decode_item* items, int cap, int32_t* seq);   // decode_kernels.hip
 void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out);   // prefill_kernels.hip

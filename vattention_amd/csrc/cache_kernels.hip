@@ -146,8 +146,10 @@ __global__ void append_kv_kernel(vattn_attn_params p) {
 // thread per (entry, K or V, kv head, 16-byte chunk): it reads ITS chunk of the kept rows (at most 8) into registers, then stores them to
 // rows row0 .. row0 + cnt - 1 — every byte is read and written by one thread only, reads before writes: no race, whatever the overlap of
 // source and destination rows.  An index outside [i, n_draft) breaks the caller's contract (strictly ascending): that row is left alone.
+// E: a cache element — uint16_t (vattn_cache_keep_rows), uint8_t (vattn_cache_keep_rows_fp8: e4m3 bytes, strides in bytes, 16 elements per chunk).
 constexpr int KEEP_MAX = 8;
-__global__ void cache_keep_rows_kernel(uint16_t* k_cache, uint16_t* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
+template <typename E>
+__global__ void cache_keep_rows_kernel(E* k_cache, E* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
                                        int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride, const int32_t* row0,
                                        const int32_t* cache_batch_idx, const int32_t* keep_idx, const int32_t* keep_cnt, int b_total, int n_draft,
                                        int h_k, int cpr) {
@@ -160,9 +162,9 @@ __global__ void cache_keep_rows_kernel(uint16_t* k_cache, uint16_t* v_cache, int
     const int slot = cache_batch_idx ? cache_batch_idx[b] : b;
     const int cnt = min(max(keep_cnt[b], 0), n_draft);
     const int64_t row_stride = is_v ? v_row_stride : k_row_stride;
-    uint16_t* base = is_v ? v_cache + (int64_t)slot * v_batch_stride + (int64_t)hk * v_head_stride
+    E* base = is_v ? v_cache + (int64_t)slot * v_batch_stride + (int64_t)hk * v_head_stride
                           : k_cache + (int64_t)slot * k_batch_stride + (int64_t)hk * k_head_stride;
-    base += (int64_t)row0[b] * row_stride + c * 8;
+    base += (int64_t)row0[b] * row_stride + c * (int)(16 / sizeof(E));
     uint4 rows[KEEP_MAX];
     bool ok[KEEP_MAX];
 #pragma unroll
@@ -360,9 +362,29 @@ int vattn_cache_keep_rows(void* k_cache, void* v_cache, int64_t k_batch_stride, 
         return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows needs 16-byte aligned rows (strides of 8 elements)");
     const int64_t total = (int64_t)b * 2 * h_k * (d / 8);
     if (total > 0x7fffffff) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows: batch too large");
-    hipLaunchKernelGGL(cache_keep_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint16_t*)k_cache, (uint16_t*)v_cache,
+    hipLaunchKernelGGL(cache_keep_rows_kernel<uint16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint16_t*)k_cache, (uint16_t*)v_cache,
                        k_batch_stride, k_row_stride, k_head_stride, v_batch_stride, v_row_stride, v_head_stride, row0, cache_batch_idx, keep_idx,
                        keep_cnt, (int)b, (int)n_draft, (int)h_k, (int)(d / 8));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
+    return VATTN_K_OK;
+}
+
+int vattn_cache_keep_rows_fp8(void* k_cache, void* v_cache, int64_t k_batch_stride, int64_t k_row_stride, int64_t k_head_stride,
+                              int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride, const int32_t* row0,
+                              const int32_t* cache_batch_idx, const int32_t* keep_idx, const int32_t* keep_cnt, int32_t b, int32_t n_draft,
+                              int32_t h_k, int32_t d, void* stream) {
+    if (!k_cache || !v_cache || !row0 || !keep_idx || !keep_cnt) return fail(VATTN_K_ERR_INVALID, "null tensor pointer");
+    if (b <= 0 || h_k <= 0 || n_draft <= 0) return fail(VATTN_K_ERR_INVALID, "cache_keep_rows_fp8: batch size, kv heads and n_draft must be positive");
+    if (n_draft > KEEP_MAX) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows_fp8 handles at most 8 draft rows per entry");
+    if (d != 64 && d != 128) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows_fp8 supports head dimensions 64 and 128");
+    if (((k_batch_stride | k_row_stride | k_head_stride | v_batch_stride | v_row_stride | v_head_stride) & 15) || ((((uintptr_t)k_cache) | ((uintptr_t)v_cache)) & 15))
+        return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows_fp8 needs 16-byte aligned rows (strides of 16 bytes)");
+    const int64_t total = (int64_t)b * 2 * h_k * (d / 16);
+    if (total > 0x7fffffff) return fail(VATTN_K_ERR_UNSUPPORTED, "cache_keep_rows_fp8: batch too large");
+    hipLaunchKernelGGL(cache_keep_rows_kernel<uint8_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint8_t*)k_cache, (uint8_t*)v_cache,
+                       k_batch_stride, k_row_stride, k_head_stride, v_batch_stride, v_row_stride, v_head_stride, row0, cache_batch_idx, keep_idx,
+                       keep_cnt, (int)b, (int)n_draft, (int)h_k, (int)(d / 16));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VATTN_K_ERR_LAUNCH, hipGetErrorString(e));
     return VATTN_K_OK;

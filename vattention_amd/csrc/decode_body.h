@@ -44,15 +44,25 @@ constexpr int DC_BN = 32;     // keys per wave tile
 // of the masked tail tiles become a per-column bit mask, loaded there; the steady-state loop is the MT one.  The mask pointer is a kernel
 // argument of these builds alone (tree_mask_arg): vattn_attn_params is frozen, and the other builds keep their argument lists.
 // FP8: the K / V cache holds OCP e4m3 bytes with one fp32 scale per kv head (vattn_fp8kv_attn_with_kvcache, include/vattn_kernels.h; one-token
-// and MT builds without WIN / TREE / ROPE) — builds of their own, the others carry no trace of it.  q, P and the MFMAs stay T: the bytes are
+// and MT builds without WIN / ROPE; beside TREE: below) — builds of their own, the others carry no trace of it.  q, P and the MFMAs stay T: the bytes are
 // widened in registers (exact: 3 mantissa bits, |x| <= 448) and the scales never touch an element — k_scale[hk] folds into sc, v_scale[hk] into
 // the final 1 / l, so partials are published scaled and the merges do not know the cache dtype.  A lane's 16-byte K load is 16 consecutive d of
 // one key row and feeds TWO k-steps: slot (g4, j) of k-step kk <-> d = 64*(kk/2) + 16*g4 + 8*(kk&1) + j (the dot product over d is order-free:
 // the Q^T fragments are loaded with the same permutation); V takes half the passes and is widened on its way into the wave-private LDS
 // layout, which the transposed reads and the PV MFMAs see unchanged.  No fused append, no fused rotation (the host quantises k_new / v_new
 // first: launch_append_fp8).  The scale pointers are a kernel argument of these builds alone, in the place of the TREE builds' mask.
+// TREE && FP8: the tree-masked multi-token form over an e4m3 cache (vattn_fp8kv_tree_attn_with_kvcache) — the product of the two: the mask only
+// touches the scores of the masked tail tiles, the cache dtype only how K / V bytes become MFMA operands and the two fp32 constants.  Builds of
+// their own again; their last argument carries both the mask words and the scales (fp8_tree_arg), the other builds keep their argument lists.
 struct no_tree_mask {};
-template <bool TREE, bool FP8 = false> using tree_mask_arg = std::conditional_t<TREE, const uint32_t*, std::conditional_t<FP8, fp8_scales, no_tree_mask>>;
+struct fp8_tree_arg { const uint32_t* mask; fp8_scales scales; };
+template <bool TREE, bool FP8 = false> using tree_mask_arg = std::conditional_t<TREE, std::conditional_t<FP8, fp8_tree_arg, const uint32_t*>, std::conditional_t<FP8, fp8_scales, no_tree_mask>>;
+// the mask words and the scales out of the last kernel argument of a build (null / empty where the build has none)
+template <bool TREE, bool FP8> __device__ __forceinline__ void unpack_mask_arg(const tree_mask_arg<TREE, FP8>& a, const uint32_t*& tmask, fp8_scales& scales) {
+    if constexpr (TREE && FP8) { tmask = a.mask; scales = a.scales; }
+    else if constexpr (TREE) tmask = a;
+    else if constexpr (FP8) scales = a;
+}
 template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,
@@ -60,7 +70,7 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
                                             const int st_mode = 0, const int st_slot = 0, const int st_lk = 0, const unsigned st_block = 0,
                                             const int tstride = 1, const uint32_t* tree_mask = nullptr, const fp8_scales scales = {}) {
     static_assert(!TREE || (MT && !WIN), "the tree mask belongs to the window-less multi-token builds");
-    static_assert(!FP8 || (!WIN && !TREE && ROPE == 0 && W == DC_WAVES && USE_TR), "the fp8 cache builds: one-token and multi-token, no window / tree mask / rotation");
+    static_assert(!FP8 || (!WIN && ROPE == 0 && W == DC_WAVES && USE_TR), "the fp8 cache builds: one-token, multi-token and tree-masked multi-token, no window / rotation");
     // st_mode != 0: a piece [item_tb, item_te) of the device-planned stream decomposition (decode_stream_kernel below).  Slot and visible
     // length come from the workgroup's plan (LDS) instead of two dependent global loads; st_mode 1 = the piece is the whole sequence: the
     // final rows are written; st_mode 2 = a partial, published as one record block at byte offset st_block of the workspace (16-byte
@@ -800,9 +810,8 @@ __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, 
 template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
 __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append, tree_mask_arg<TREE, FP8> tree_mask = {}) {
     const uint32_t* tmask = nullptr;
-    if constexpr (TREE) tmask = tree_mask;
     fp8_scales scales = {};
-    if constexpr (FP8) scales = tree_mask;
+    unpack_mask_arg<TREE, FP8>(tree_mask, tmask, scales);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_plan[3 * DC_MAXB];                // stream mode: the plan, for the pieces after the first
     const int tid = threadIdx.x;
@@ -894,9 +903,8 @@ template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1,
 __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append, tree_mask_arg<TREE, FP8> tree_mask = {}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const uint32_t* tmask = nullptr;
-    if constexpr (TREE) tmask = tree_mask;
     fp8_scales scales = {};
-    if constexpr (FP8) scales = tree_mask;
+    unpack_mask_arg<TREE, FP8>(tree_mask, tmask, scales);
     int split, hk, gb, b;
     if (!MT && !FP8 && p.split_items != nullptr) {          // (host items: the one-token form only, 2-byte caches only)
         // length-balanced plan: blockIdx.x = work item (a piece of ONE sequence), blockIdx.y = (kv head, head-block group)

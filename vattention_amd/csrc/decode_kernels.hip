@@ -221,10 +221,11 @@ template <int HD, bool MT, bool FP8> static decode_launch begin_decode_launch(co
     }
     return {(size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2, fused_append};
 }
-// The last kernel argument of every build: the mask words of the TREE builds, the scale pointers of the FP8 builds, an empty struct for the
-// others (decode_body.h, tree_mask_arg)
+// The last kernel argument of every build: the mask words of the TREE builds, the scale pointers of the FP8 builds, both for the TREE && FP8
+// builds, an empty struct for the others (decode_body.h, tree_mask_arg)
 template <bool TREE, bool FP8> static tree_mask_arg<TREE, FP8> mask_arg(const decode_extra& x) {
-    if constexpr (TREE) return x.tree_mask;
+    if constexpr (TREE && FP8) return fp8_tree_arg{x.tree_mask, fp8_scales{x.k_scale, x.v_scale}};
+    else if constexpr (TREE) return x.tree_mask;
     else if constexpr (FP8) return fp8_scales{x.k_scale, x.v_scale};
     else return {};
 }
@@ -276,11 +277,12 @@ template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> in
 // no window — the multi-token launch of the same block, planners, grids, append and merges, on the TREE builds), else one token or the
 // multi-token form (the caller checked multitoken_form(p)), with or without a window; then one or two head blocks per workgroup.  FP8
 // (vattn_fp8kv_attn_with_kvcache: the caller checked its gate — decode_form(p), no window): one token or the multi-token form on the FP8 builds.
+// TREE && FP8 (vattn_fp8kv_tree_attn_with_kvcache: the caller checked both gates): the TREE launch on the builds that carry both switches.
 template <typename T, int HD, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_w(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
     return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, WIN, MT, TREE, FP8>(p, st, x) : launch_decode_nb<T, HD, 1, WIN, MT, TREE, FP8>(p, st, x);
 }
 template <typename T, int HD, bool TREE, bool FP8> int launch_decode_t(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
-    if constexpr (TREE) return launch_decode_w<T, HD, false, true, true, false>(p, st, x);
+    if constexpr (TREE) return launch_decode_w<T, HD, false, true, true, FP8>(p, st, x);
     else if constexpr (FP8) return p->seqlen_q == 1 ? launch_decode_w<T, HD, false, false, false, true>(p, st, x) : launch_decode_w<T, HD, false, true, false, true>(p, st, x);
     else {
         const bool win = p->window_left_plus1 > 0;
@@ -288,7 +290,7 @@ template <typename T, int HD, bool TREE, bool FP8> int launch_decode_t(const vat
         return win ? launch_decode_w<T, HD, true, true, false, false>(p, st, x) : launch_decode_w<T, HD, false, true, false, false>(p, st, x);
     }
 }
-// dtype x head dimension: the one ladder of the three entry points
+// dtype x head dimension: the one ladder of the four entry points
 template <bool TREE, bool FP8> static int launch_decode_dtype_hd(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
     const bool f16 = p->dtype == VATTN_DTYPE_F16;
     if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64, TREE, FP8>(p, st, x) : launch_decode_t<__bf16, 64, TREE, FP8>(p, st, x);
@@ -298,6 +300,9 @@ int launch_decode_form(const vattn_attn_params* p, hipStream_t st) { return laun
 int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) { return launch_decode_dtype_hd<true, false>(p, st, {tree_mask, nullptr, nullptr}); }
 int launch_fp8kv_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st) {
     return launch_decode_dtype_hd<false, true>(p, st, {nullptr, k_scale, v_scale});
+}
+int launch_fp8kv_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale, hipStream_t st) {
+    return launch_decode_dtype_hd<true, true>(p, st, {tree_mask, k_scale, v_scale});
 }
 
 // Length-balanced split of a ragged decode batch (include/vattn_kernels.h, vattn_decode_plan).  Every sequence is cut into pieces of at

@@ -35,6 +35,8 @@ Deliberate difference: the reference raises "If key is supplied, 
 than Hq/Hkv tokens) and its wrapper then silently returns unwritten output; this shim raises that
 message only when the new keys genuinely do not fit, and otherwise always computes.
 
+Tree-masked multi-token decode over an fp8 cache: `flash_attn_fp8kv_tree_with_kvcache` — the two extensions multiplied.
+
 Call path:  flash_attn_with_kvcache / flash_attn_tree_with_kvcache (varlen: its own layout, the same helpers)
   -> _build_block: the shared checks, `out` / LSE, the tensor, stride and shape fields of an AttnParams
   -> the entry's own fields (window, causal, variant, rotary, hints, plans | the Sq rule, the mask words) and _set_scalars
@@ -183,16 +185,20 @@ def relaunch(p, q_ptr: int, k_new_ptr: int, v_new_ptr: int, out_ptr: int, k_cach
 def _issue(p, dev, lib, need=None, mask=None, scales=None, fp8_prefill=False):
     """The one launch: the workspace the call needs (asked of the library unless `need` is known: relaunch) from the per-(device, stream)
     cache, the call on the current stream — the tree-masked entry point iff `mask` is given, the fp8-cache entry point iff `scales` =
-    (k_scale, v_scale; either may be None: the library refuses that; fp8_prefill: its prefill-form sibling) — and its return code as an
-    exception (the -10 of those entries names the rule of their gate that the block breaks: NotImplementedError).  Returns the workspace need."""
+    (k_scale, v_scale; either may be None: the library refuses that; fp8_prefill: its prefill-form sibling), the tree-masked entry point over
+    an fp8 cache iff both are given — and its return code as an exception (the -10 of those entries names the rule of their gate that the
+    block breaks: NotImplementedError).  Returns the workspace need."""
     if need is None:
-        need = (lib.vattn_tree_attn_workspace_bytes if mask is not None else
+        need = (lib.vattn_fp8kv_tree_attn_workspace_bytes if mask is not None and scales is not None else
+                lib.vattn_tree_attn_workspace_bytes if mask is not None else
                 (lib.vattn_fp8kv_prefill_workspace_bytes if fp8_prefill else lib.vattn_fp8kv_attn_workspace_bytes) if scales is not None
                 else lib.vattn_attn_workspace_bytes)(C.byref(p))
     st = K.current_stream_ptr(dev)
     if need:
         p.workspace = _workspace(need, dev, st).data_ptr()   # kept alive by the per-(device, stream) cache until a larger one replaces it
-    if mask is not None:
+    if mask is not None and scales is not None:
+        rc = lib.vattn_fp8kv_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), *(s.data_ptr() if s is not None else None for s in scales), st)
+    elif mask is not None:
         rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
     elif scales is not None:
         rc = (lib.vattn_fp8kv_prefill_with_kvcache if fp8_prefill else lib.vattn_fp8kv_attn_with_kvcache)(
@@ -445,6 +451,30 @@ def flash_attn_fp8kv_with_kvcache(q, k_cache, v_cache, k_scale, v_scale, k=None,
     return (out, lse) if return_softmax_lse else out
 
 
+def flash_attn_fp8kv_tree_with_kvcache(q, k_cache, v_cache, k_scale, v_scale, tree_mask, k=None, v=None,
+                                       cache_seqlens: Optional[Union[int, torch.Tensor]] = None, cache_batch_idx: Optional[torch.Tensor] = None,
+                                       softmax_scale=None, return_softmax_lse=False, _num_splits: int = 0):
+    """MI355X extension (include/vattn_kernels.h, "tree-masked multi-token form over an fp8 cache"): flash_attn_tree_with_kvcache over a
+    float8_e4m3fn cache — verify a draft TREE of Sq = 2..8 nodes per entry in ONE pass over e4m3 K/V.  q [B, Sq, Hq, D] (fp16 / bf16, also
+    the dtype of out and of k / v) with Sq * (Hq / Hkv) <= 64; caches, k_scale / v_scale as in flash_attn_fp8kv_with_kvcache; tree_mask as in
+    flash_attn_tree_with_kvcache (int32 / uint32 [B, Sq] bit words or a bool [B, Sq, Sq] / [Sq, Sq] tensor).  `k` / `v` [B, Sq, Hkv, D] are
+    quantised and appended at cache_seqlens first (cache_ops.cache_flat_fp8's bytes), or the nodes' rows are already in the cache; node t
+    sees every key below base = Lk - Sq and draft key base + s iff the mask says so, as stored * scale.  No causal flag, window or rotary:
+    calls outside the gate raise NotImplementedError naming the rule.  `_num_splits` < 0: the decode kernels' forced grids (tests, A/B).
+    Mask and scales are read by the kernels, never by the host: works under graph capture like decode.  Afterwards `cache_ops.keep_rows`
+    makes the accepted path contiguous."""
+    p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, None, return_softmax_lse,
+                                                              cache_dtype=torch.float8_e4m3fn)
+    if not 2 <= Sq <= 8:
+        raise NotImplementedError("a tree mask needs 2 <= seqlen_q <= 8 (one mask word of 8 bits per query token); got %d" % Sq)
+    _check_scales(k_scale, v_scale, p.h_k)
+    mask = _pack_tree_mask(tree_mask, B, Sq, dev)
+    _set_scalars(p, keep[0], _num_splits, softmax_scale)      # (is_causal / variant stay 0: the mask is the rule, the product library the only one)
+    _issue(p, dev, K.klib(), None, mask, (k_scale, v_scale))
+    counters["fp8kv_tree_calls"] += 1
+    return (out, lse) if return_softmax_lse else out
+
+
 def _check_scales(k_scale, v_scale, Hkv):
     for s in (k_scale, v_scale):      # (None reaches the library, which refuses it)
         if s is not None and (not s.is_cuda or s.dtype != torch.float32 or s.shape != (Hkv,) or not s.is_contiguous()):
@@ -494,7 +524,7 @@ _plan_cache = {}      # (shapes, lengths, device, stream) -> _PrefillPlan; a few
 # with other lengths in between gets plans sized for the wrong lengths; False switches the lookup off (the view's row count then bounds
 # the plan, FlashAttention's own rule).
 USE_PAGE_MANAGER_LENGTHS = True
-counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "fp8kv_decode_calls": 0, "fp8kv_prefill_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
+counters = {"prefill_calls": 0, "multitoken_decode_calls": 0, "tree_decode_calls": 0, "fp8kv_decode_calls": 0, "fp8kv_prefill_calls": 0, "fp8kv_tree_calls": 0, "lengths_from_page_manager": 0, "plan_built": 0, "plan_cache_hit": 0, "work_list_attached": 0}      # introspection (tools/, tests)
 
 
 def _cached_prefill_plan(p, klens, dev):

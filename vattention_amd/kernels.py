@@ -117,6 +117,14 @@ def _bind(lib):
     lib.vattn_fp8kv_prefill_workspace_bytes.argtypes = [C.POINTER(AttnParams)]
     lib.vattn_fp8kv_prefill_plan_describe.restype = i32
     lib.vattn_fp8kv_prefill_plan_describe.argtypes = [C.POINTER(AttnParams), C.POINTER(PlanDesc)]
+    lib.vattn_fp8kv_tree_attn_with_kvcache.restype = i32
+    lib.vattn_fp8kv_tree_attn_with_kvcache.argtypes = [C.POINTER(AttnParams), vp, vp, vp, vp]
+    lib.vattn_fp8kv_tree_attn_workspace_bytes.restype = C.c_size_t
+    lib.vattn_fp8kv_tree_attn_workspace_bytes.argtypes = [C.POINTER(AttnParams)]
+    lib.vattn_fp8kv_tree_attn_plan_describe.restype = i32
+    lib.vattn_fp8kv_tree_attn_plan_describe.argtypes = [C.POINTER(AttnParams), C.POINTER(PlanDesc)]
+    lib.vattn_cache_keep_rows_fp8.restype = i32
+    lib.vattn_cache_keep_rows_fp8.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.vattn_cache_flat_fp8.restype = i32
     lib.vattn_cache_flat_fp8.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, vp, vp, vp]
     lib.vattn_decode_plan.restype = i32
@@ -154,14 +162,15 @@ def klib_for(variant: int):
     return klib_lab() if needs_lab(int(variant)) else klib()
 
 
-def describe(p, lib=None, tree=False, fp8kv=False, fp8kv_prefill=False) -> dict:
+def describe(p, lib=None, tree=False, fp8kv=False, fp8kv_prefill=False, fp8kv_tree=False) -> dict:
     """The launch plan of parameter block `p` (vattn_attn_plan_describe): pure host arithmetic.  tree: of its tree-masked call
     (vattn_tree_attn_plan_describe) — the multi-token call's plan, or an error naming the rule of the gate the block breaks.  fp8kv: of its
     call over an fp8 cache (vattn_fp8kv_attn_plan_describe) — the 2-byte call's plan for the same block, or an error naming the rule.
-    fp8kv_prefill: of its prefill call over an fp8 cache (vattn_fp8kv_prefill_plan_describe) — the 2-byte call's plan without prefill64."""
+    fp8kv_prefill: of its prefill call over an fp8 cache (vattn_fp8kv_prefill_plan_describe) — the 2-byte call's plan without prefill64.
+    fp8kv_tree: of its tree-masked call over an fp8 cache (vattn_fp8kv_tree_attn_plan_describe) — the tree call's answer for the same block."""
     lib = lib or klib()
     d = PlanDesc()
-    fn = (lib.vattn_tree_attn_plan_describe if tree else lib.vattn_fp8kv_attn_plan_describe if fp8kv else
+    fn = (lib.vattn_fp8kv_tree_attn_plan_describe if fp8kv_tree else lib.vattn_tree_attn_plan_describe if tree else lib.vattn_fp8kv_attn_plan_describe if fp8kv else
           lib.vattn_fp8kv_prefill_plan_describe if fp8kv_prefill else lib.vattn_attn_plan_describe)
     rc = fn(C.byref(p), C.byref(d))
     if rc != 0:
@@ -175,6 +184,10 @@ def describe_fp8kv(p, lib=None) -> dict:
 
 def describe_fp8kv_prefill(p, lib=None) -> dict:
     return describe(p, lib, fp8kv_prefill=True)
+
+
+def describe_fp8kv_tree(p, lib=None) -> dict:
+    return describe(p, lib, fp8kv_tree=True)
 
 
 def describe_tree(p, lib=None) -> dict:
