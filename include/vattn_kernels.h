@@ -82,7 +82,10 @@ typedef struct vattn_attn_params {
      * kernel (/root/reference/sarathi-lean/csrc/pos_encoding_kernels.cu:9-77, every product and the sum rounded to the I/O
      * dtype).  Layout = the reference's cos_sin_cache: row `pos` holds cos[0 .. rotary_dim/2) then sin[0 .. rotary_dim/2), I/O
      * dtype, rows rotary_row_stride elements apart.  Token i of batch entry b sits at position cache_seqlens[b] + i (new keys)
-     * resp. (visible keys - seqlen_q) + i (queries), i.e. the call-site convention of the wrapper.  rotary_dim must equal d. */
+     * resp. (visible keys - seqlen_q) + i (queries), i.e. the call-site convention of the wrapper.  rotary_dim must equal d.
+     * A query row whose position is NEGATIVE (an entry without a visible key; seqlen_q > visible keys) has no table row: it is left
+     * un-rotated and no table row is read for it.  With is_causal or a window such a row sees no key (output 0, LSE +inf); in a non-causal
+     * call it attends to every key with its un-rotated q — a caller that wants those rows rotated passes at most as many rows as keys. */
     const void* rotary_cos_sin;
     int64_t rotary_row_stride;
     int32_t rotary_dim;

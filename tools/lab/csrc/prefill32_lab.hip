@@ -193,7 +193,7 @@ __global__ __launch_bounds__(512, 1) void prefill32_kernel(vattn_attn_params p, 
             if (my_q < Sq) v = *(const uint4*)(qptr + 16 * kk + 8 * g);
             raw[kk] = as_v8<V8>(v);
         }
-        if (p.rotary_cos_sin && my_q < Sq) {
+        if (p.rotary_cos_sin && my_q < Sq && off + my_q >= 0) {      // (a row in front of position 0 stays un-rotated: include/vattn_kernels.h)
             // fused RoPE: query row i sits at position (visible keys - Sq) + i; an element and its partner d + 64 live in the same lane
 #pragma unroll
             for (int kk = 0; kk < KK / 2; kk++) {

@@ -84,7 +84,7 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
             if (my_q < Sq) v = *(const uint4*)(qptr + 16 * kk + 8 * g);
             qf[qc][kk] = as_v8<V8>(v);
         }
-        if (p.rotary_cos_sin && my_q < Sq) {
+        if (p.rotary_cos_sin && my_q < Sq && off + my_q >= 0) {      // (a row in front of position 0 stays un-rotated: include/vattn_kernels.h)
             // fused RoPE: query row i sits at position (visible keys - Sq) + i; slot (g, j) of k-step kk is element 16*kk + 8*g + j,
             // so an element and its partner d + HD/2 live in the same lane (k-steps kk and kk + KK/2)
 #pragma unroll

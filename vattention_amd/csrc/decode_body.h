@@ -152,8 +152,9 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     }
     // fused RoPE (include/vattn_kernels.h): the query token sits at position Lk - 1; slot (g4, j) of k-step kk is element
     // d = 32*kk + 8*g4 + j, so element d and its partner d + HD/2 live in the SAME lane (k-steps kk and kk + KK/2)
+    // (an entry without a visible key has no position Lk - 1: its q is never used and stays un-rotated — no table row is read for it)
     const bool rope = ROPE < 0 ? p.rotary_cos_sin != nullptr : ROPE == 1;
-    if (rope) {
+    if (rope && Lk > 0) {
 #pragma unroll
         for (int kk = 0; kk < KK / 2; kk++) {
             V8 c, s;

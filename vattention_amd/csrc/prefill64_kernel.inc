@@ -145,8 +145,10 @@ __global__ __launch_bounds__(256, 1) void P64_KERNEL_NAME(vattn_attn_params p, i
             }
             raw[kk] = as_v8<V8>(v);
         }
-        if (p.rotary_cos_sin && my_q < Sq) {
+        if (p.rotary_cos_sin && my_q < Sq && off + my_q >= 0) {
             // fused RoPE: query row i sits at position (visible keys - Sq) + i; an element and its partner d + 64 live in the same lane
+            // (a row in front of position 0 — Sq > Lk — has no table row: it stays un-rotated and none is read; causal / windowed: it
+            // sees no key; non-causal: it attends with its un-rotated q — include/vattn_kernels.h)
 #pragma unroll
             for (int kk = 0; kk < KK / 2; kk++) {
                 V8 c, s;

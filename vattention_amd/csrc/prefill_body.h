@@ -91,9 +91,11 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
             if (my_q < Sq) v = *(const uint4*)(qptr + 16 * kk + 8 * g);
             qf[qc][kk] = as_v8<V8>(v);
         }
-        if (p.rotary_cos_sin && my_q < Sq) {
+        if (p.rotary_cos_sin && my_q < Sq && off + my_q >= 0) {
             // fused RoPE: query row i sits at position (visible keys - Sq) + i; slot (g, j) of k-step kk is element 16*kk + 8*g + j,
-            // so an element and its partner d + HD/2 live in the same lane (k-steps kk and kk + KK/2)
+            // so an element and its partner d + HD/2 live in the same lane (k-steps kk and kk + KK/2).  A row in front of position 0
+            // (Sq > Lk) has no table row: it stays un-rotated and none is read (include/vattn_kernels.h; causal / windowed: it sees no
+            // key; non-causal: it attends with its un-rotated q)
 #pragma unroll
             for (int kk = 0; kk < KK / 2; kk++) {
                 V8 c, s;
