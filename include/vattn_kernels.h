@@ -364,6 +364,35 @@ int vattn_fp8kv_prefill_with_kvcache(const vattn_attn_params* p, const float* k_
 size_t vattn_fp8kv_prefill_workspace_bytes(const vattn_attn_params* p);
 int vattn_fp8kv_prefill_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out);
 
+/* LOGIT SOFT-CAPPING (Gemma-2 / Gemma-3: attn_logit_softcapping): scores = softcap * tanh(q.k * softmax_scale / softcap), the `softcap` of the
+ * reference's operator (flash_api.cpp:105-113, apply_softcap in flash_fwd_kernel.h:26-30).  Additive: vattn_attn_params and VATTN_KERNELS_ABI
+ * are unchanged, the cap travels BESIDE the parameter block as an extra argument of builds of the decode kernels and of the register-staged
+ * prefill kernels of their own; every other kernel, entry point and refusal is what it was.
+ * ARITHMETIC (one answer for every input, the reference's order of operations): (1) the host forms pre = softmax_scale / softcap by IEEE fp32
+ * division; (2) in the kernel t = tanh(s * pre) is taken on the fp32 MFMA accumulator s = q.k BEFORE any mask is applied — a masked score stays
+ * -inf (tanh(-inf) = -1 would unmask it); (3) tanh(x) = 1 - 2 / (1 + exp2(2 log2e x)) on the hardware exp2 and reciprocal, evaluated as
+ * fma(-2, rcp(1 + exp2(s * k2)), 1) with k2 = pre * 2 log2e formed once per kernel in fp32: branch-free, and +-1 at the limits without a select;
+ * (4) the online softmax runs on t with softcap as its scale (sc = softcap * log2e where the plain kernels use softmax_scale * log2e): running
+ * max, rescaling, the cross-wave merge and published partials follow from that; (5) softmax_lse is the natural log of sum exp(softcap * t); a
+ * row without a visible key gives 0 and LSE +inf, as everywhere.  ERROR: that tanh expression in IEEE fp32 has absolute error 1.9e-7 on
+ * [-12, 12]; a capped logit is off by about softcap * 2e-7 — 1e-5 at softcap 50 — and the error GROWS WITH THE CAP: a huge cap is not a way
+ * to spell "no cap" (pass 0).  The hardware exp2 / reciprocal are 1-ulp approximations; tests/test_gpu_softcap.py's LSE checks measure them.
+ * softcap == 0.0f delegates to vattn_flash_attn_with_kvcache(p, stream), unchanged and bit-identical; negative, NaN or infinite softcap is
+ * VATTN_K_ERR_INVALID, and so is one so small (a denormal) that pre = softmax_scale / softcap is no finite fp32 number.
+ * GATE (softcap > 0): the one-token decode form; the multi-token form (its gate above), causal or not; the prefill form on the register-staged
+ * kernels (8 / 4 waves x 32 rows, d 64 / 128, f16 / bf16): causal or not, cache_batch_idx, softmax_lse, KV split, batched chunks (q_start /
+ * q_lens) — each WITH OR WITHOUT window_left_plus1 under the window's rules and no-read contract above; k_new / v_new behave as in the plain
+ * call for the same block (one decode row inside the attention kernel, otherwise an append launch in front of it).  Refused with
+ * VATTN_K_ERR_UNSUPPORTED and a message that names the rule: rotary_cos_sin (rotate first: vattn_rotary_embedding / vattn_cache_flat_rope),
+ * split_items, pf_items / pf_num_wg, explicit tiling 7 (prefill64 has no softcap build), d other than 64 / 128, a -DVATTN_LAB build.  There is
+ * no tree-masked, fp8 or hybrid entry point with a cap.
+ * PLAN: that of vattn_flash_attn_with_kvcache for the same block with its prefill64 branch skipped (the rule of vattn_fp8kv_prefill_*): grids,
+ * stream decomposition, record layouts, merge / combine kernels and workspace sizes are the plain call's; partials are fp32 and do not know
+ * about the cap.  _workspace_bytes / _plan_describe answer what this call gets (0 / an error outside the gate; softcap == 0: the plain call's). */
+int vattn_softcap_attn_with_kvcache(const vattn_attn_params* p, float softcap, void* stream);
+size_t vattn_softcap_attn_workspace_bytes(const vattn_attn_params* p, float softcap);
+int vattn_softcap_attn_plan_describe(const vattn_attn_params* p, float softcap, vattn_plan_desc* out);
+
 /* Fused prefill || decode for a hybrid batch (replaces the reference's POD-Attention entry point
  * /root/reference/pod_attn/pod_attn/flash_attn_interface.py true_fused_attn_with_kvcache, call site
  * /root/reference/sarathi-lean/sarathi/model_executor/attention/vattention_flashattention_pod_wrapper.py:121-203): ONE launch of

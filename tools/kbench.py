@@ -7,7 +7,10 @@ usage: python tools/kbench.py [prefill] [decode] [--variant N]
        python tools/kbench.py decode --kv-fp8 [--only NAMES] / multitoken --kv-fp8 --mt ...   (the same call over an fp8 (e4m3) cache —
                                                                           vattn_fp8kv_attn_with_kvcache — beside the 2-byte call, alternating, over rotating caches)
        python tools/kbench.py prefill --kv-fp8 [--only NAMES] [--bf16]   (a chunk on a prefix through vattn_fp8kv_prefill_with_kvcache beside the 2-byte call
-                                                                          forced to the same tiling and split, and the 2-byte call under its default plan)"""
+                                                                          forced to the same tiling and split, and the 2-byte call under its default plan)
+       python tools/kbench.py decode --softcap X [--only NAMES] / multitoken --softcap X --mt ... / prefill --softcap X [--only NAMES]   (the call with logit
+                                                                          soft-capping — vattn_softcap_attn_with_kvcache — beside the plain call, alternating, over rotating
+                                                                          caches; prefill: beside the plain call on the SAME tiling and split, and under its default plan)"""
 import ctypes as C
 import os
 import sys
@@ -360,6 +363,91 @@ def fp8_prefill_ab(name, Hq, Hkv, n, c):
     print("    ratios: (a) / (b) = %.3f   (a) / (c) = %.3f   (b) / (c) = %.3f" % (med[0] / med[1], med[0] / med[2], med[1] / med[2]), flush=True)
 
 
+def _ab_windows(runs, iters, lib):
+    """median and the five alternating windows (us per call) of every (call, blocks) pair of `runs`, after one warm-up window each"""
+    def window(call, ps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            for pp, _k in ps:
+                if call(pp) != 0:
+                    raise RuntimeError(K.last_error(lib))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / (iters * len(ps)) * 1e3
+    for call, ps in runs:
+        window(call, ps)
+    t = [[] for _ in runs]
+    for _rep in range(5):
+        for i, (call, ps) in enumerate(runs):
+            t[i].append(window(call, ps))
+    return [sorted(x)[2] for x in t], t
+
+
+def softcap_ab(name, B, sq, Hq, Hkv, ctx, cap, ragged=False):
+    """--softcap X (decode, multitoken): ONE block (q [B, sq, Hq, 128], sq new rows appended at ctx - sq) through vattn_flash_attn_with_kvcache
+    and through vattn_softcap_attn_with_kvcache(softcap = X), ALTERNATING in one process over the same R rotating caches (R x bytes >= 1.5 GB:
+    nothing is served from the 256 MiB Infinity Cache), warmed up, five windows each.  The plan is the same by construction (asserted)."""
+    torch.manual_seed(0)
+    lib, st = K.klib(), torch.cuda.current_stream().cuda_stream
+    by16 = B * 2.0 * ctx * Hkv * 128 * 2
+    R = max(2, int(1.5e9 // by16) + 1)
+    lens = [ctx - sq - (i * 7919 % (ctx - ctx // 8)) for i in range(B)] if ragged else [ctx - sq] * B
+    cl = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    idx = torch.arange(B, dtype=torch.int32, device=DEV)
+    q = torch.randn(B, sq, Hq, 128, device=DEV, dtype=DTYPE)
+    kn, vn = torch.randn(B, sq, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, sq, Hkv, 128, device=DEV, dtype=DTYPE)
+    ps = []
+    for _ in range(R):
+        kc, vc = torch.randn(B, ctx, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(B, ctx, Hkv, 128, device=DEV, dtype=DTYPE)
+        ps.append(params(q, kc, vc, cl, idx, kn, vn))
+    d = K.describe_softcap(ps[0][0], cap)
+    assert d == K.describe(ps[0][0])
+    plain = lambda pp: lib.vattn_flash_attn_with_kvcache(C.byref(pp), st)
+    capped = lambda pp: lib.vattn_softcap_attn_with_kvcache(C.byref(pp), cap, st)
+    med, t = _ab_windows(((plain, ps), (capped, ps)), max(2, 60 // R + 1), lib)
+    by = sum(n + sq for n in lens) * 2.0 * Hkv * 128 * 2 + 2.0 * B * sq * Hq * 128 * 2
+    print("  %-22s B=%3d sq=%d ctx=%6d Hq=%2d Hkv=%d%s  path %d tiling %d wg %d, %d rotating caches" % (name, B, sq, ctx, Hq, Hkv, " ragged" if ragged else "", d["path"], d["tiling"], d["workgroups"], R))
+    for tag, m, x in (("plain        ", med[0], t[0]), ("softcap %-5g" % cap, med[1], t[1])):
+        print("    %s: median %8.1f us  (5 windows: %s; spread %.1f%%)  %7.1f GB/s = %.1f%% of 8000" % (
+            tag, m, " ".join("%.1f" % y for y in x), 100.0 * (max(x) - min(x)) / m, by / m / 1e3, by / m / 1e3 / 80))
+    print("    ratio softcap / plain : %.3f" % (med[1] / med[0]), flush=True)
+
+
+def softcap_prefill_ab(name, Hq, Hkv, n, c, cap):
+    """prefill --softcap X: ONE block — a causal chunk of n rows whose keys [0, c + n) are in the cache — timed three ways, ALTERNATING in one
+    process over R rotating caches, warmed up, five windows each: (a) vattn_softcap_attn_with_kvcache; (b) the plain call FORCED to (a)'s
+    tiling and split count — the yardstick of the softcap builds: the same grid, the same kernel but for the tanh; (c) the plain call under
+    its default plan (prefill64 where the planner takes it): what a caller pays for prefill64 having no softcap build."""
+    torch.manual_seed(0)
+    lib, st = K.klib(), torch.cuda.current_stream().cuda_stream
+    rows = c + n
+    R = min(24, max(2, int(1.5e9 // (2.0 * rows * Hkv * 128 * 2)) + 1))
+    cl = torch.tensor([rows], dtype=torch.int32, device=DEV)
+    q = torch.randn(1, n, Hq, 128, device=DEV, dtype=DTYPE)
+    pa, pb, pc = [], [], []
+    for _ in range(R):
+        kc, vc = torch.randn(1, rows, Hkv, 128, device=DEV, dtype=DTYPE), torch.randn(1, rows, Hkv, 128, device=DEV, dtype=DTYPE)
+        p, keep = params(q, kc, vc, cl)
+        da = K.describe_softcap(p, cap)
+        w = torch.empty(da["workspace_bytes"] // 4 + 1, dtype=torch.float32, device=DEV)      # (this call's own need: its plan has no prefill64)
+        p.workspace = w.data_ptr()
+        pa.append((p, keep + [w]))
+        pb.append(params(q, kc, vc, cl, splits=da["nsplit"], variant=da["tiling"] << 1))
+        pc.append(params(q, kc, vc, cl))
+    db, dc = K.describe(pb[0][0]), K.describe(pc[0][0])
+    assert (db["tiling"], db["nsplit"], db["workgroups"]) == (da["tiling"], da["nsplit"], da["workgroups"]), (da, db)
+    plain = lambda pp: lib.vattn_flash_attn_with_kvcache(C.byref(pp), st)
+    capped = lambda pp: lib.vattn_softcap_attn_with_kvcache(C.byref(pp), cap, st)
+    med, t = _ab_windows(((capped, pa), (plain, pb), (plain, pc)), max(1, 24 // R), lib)
+    fl = 4.0 * Hq * 128 * (n * c + n * (n + 1) / 2)
+    print("  %-26s n=%d c=%d Hq=%2d Hkv=%d, %s, %d rotating caches" % (name, n, c, Hq, Hkv, "bf16" if DTYPE == torch.bfloat16 else "fp16", R))
+    for tag, d, m, x in (("(a) softcap %-5g         " % cap, da, med[0], t[0]), ("(b) plain, (a)'s plan    ", db, med[1], t[1]), ("(c) plain, default plan  ", dc, med[2], t[2])):
+        print("    %s tiling %d nsplit %d wg %4d : median %8.1f us  (5 windows: %s; spread %.1f%%)  %7.1f TFLOP/s" % (
+            tag, d["tiling"], d["nsplit"], d["workgroups"], m, " ".join("%.1f" % y for y in x), 100.0 * (max(x) - min(x)) / m, fl / m / 1e6))
+    print("    ratios: (a) / (b) = %.3f   (a) / (c) = %.3f   (b) / (c) = %.3f" % (med[0] / med[1], med[0] / med[2], med[1] / med[2]), flush=True)
+
+
 def multitoken(B, sq, Hq, Hkv, ctx, ragged, base_path):
     """The multi-token decode call (q [B, sq, Hq, 128] against `ctx` cached tokens, the sq new rows appended) on caches that ROTATE (as
     --rotate: the Infinity Cache serves no repeat): this tree, the one-token decode step of the same batch, the prefill form of the same
@@ -444,6 +532,14 @@ DTYPE = torch.float16
 SPLITS = (0,)
 PF_SPLITS = 0
 TREE = False
+SOFTCAP = 0.0
+# the shapes of the A/B switches (--kv-fp8, --softcap): prefill (name, Hq, Hkv, chunk rows, cached rows), decode (name, Hq, Hkv, B, context);
+# --softcap adds the model family that caps its logits
+PF_AB_SHAPES = [("yi6b chunk2k@30k", 32, 4, 2048, 30720), ("llama70b/tp8 chunk2k@30k", 8, 1, 2048, 30720), ("yi6b chunk4k@28k", 32, 4, 4096, 28672),
+                ("llama8b chunk512@8k", 32, 8, 512, 7680)]
+DC_AB_SHAPES = [("llama8b B16@32k", 32, 8, 16, 32768), ("llama8b B1@128k", 32, 8, 1, 131072), ("yi6b B16@32k", 32, 4, 16, 32768),
+                ("llama8b B64@8k", 32, 8, 64, 8192), ("llama70b/tp8 B64@32k", 8, 1, 64, 32768), ("mqa G32 B16@16k", 32, 1, 16, 16384)]
+GEMMA2_PF_SHAPE, GEMMA2_DC_SHAPE = ("gemma2-27b chunk2k@30k", 32, 16, 2048, 30720), ("gemma2-27b B16@32k", 32, 16, 16, 32768)
 
 if __name__ == "__main__":
     variant = 0
@@ -467,6 +563,10 @@ if __name__ == "__main__":
         ONLY = sys.argv[sys.argv.index("--only") + 1]
     if "--variant" in sys.argv:
         variant = int(sys.argv[sys.argv.index("--variant") + 1])
+    if "--softcap" in sys.argv:
+        SOFTCAP = float(sys.argv[sys.argv.index("--softcap") + 1])
+        if not SOFTCAP > 0:
+            sys.exit("kbench: --softcap takes a cap > 0")
     VARIANTS = [variant] if "--variant" in sys.argv else [0, 8, 12]
     if "--variants" in sys.argv:
         VARIANTS = [int(x) for x in sys.argv[sys.argv.index("--variants") + 1].split(",")]
@@ -485,7 +585,10 @@ if __name__ == "__main__":
             sys.exit("kbench multitoken: give at least one --mt B,sq,Hq,Hkv,ctx[,ragged]")
         torch.zeros(1, device=DEV)
         for dims, ragged in shapes:
-            if "--kv-fp8" in sys.argv and TREE:          # the fp8 tree entry beside the fp8 causal call and the 2-byte tree call
+            if SOFTCAP:
+                B_, sq_, Hq_, Hkv_, ctx_ = dims
+                softcap_ab("multi-token", B_, sq_, Hq_, Hkv_, ctx_ + sq_, SOFTCAP, ragged)
+            elif "--kv-fp8" in sys.argv and TREE:          # the fp8 tree entry beside the fp8 causal call and the 2-byte tree call
                 B_, sq_, Hq_, Hkv_, ctx_ = dims
                 fp8_tree_ab(B_, sq_, Hq_, Hkv_, ctx_ + sq_, ragged)
             elif "--kv-fp8" in sys.argv:
@@ -496,10 +599,23 @@ if __name__ == "__main__":
         sys.exit(0)
     what = [a for a in sys.argv[1:] if a in ("prefill", "decode")] or ["prefill", "decode"]
     torch.zeros(1, device=DEV)
+    if SOFTCAP:
+        if "prefill" in what:
+            print("== prefill (causal chunk n against c cached) with and without logit soft-capping (cap %g), D=128 ==" % SOFTCAP)
+            for name, Hq, Hkv, n, c in PF_AB_SHAPES + [GEMMA2_PF_SHAPE]:
+                if (ONLY and not any(o.strip() in name for o in ONLY.split(","))) or (not ONLY and "chunk2k@30k" not in name):
+                    continue
+                softcap_prefill_ab(name, Hq, Hkv, n, c, SOFTCAP)
+        if "decode" in what:
+            print("== decode (Sq=1, append + split-KV + combine) with and without logit soft-capping (cap %g), %s, D=128 ==" % (SOFTCAP, "bf16" if DTYPE == torch.bfloat16 else "fp16"))
+            for name, Hq, Hkv, B, ctx in DC_AB_SHAPES + [GEMMA2_DC_SHAPE]:
+                if (ONLY and not any(o.strip() in name for o in ONLY.split(","))) or (not ONLY and "B16@32k" not in name):
+                    continue
+                softcap_ab(name, B, 1, Hq, Hkv, ctx, SOFTCAP)
+        sys.exit(0)
     if "prefill" in what and "--kv-fp8" in sys.argv:
         print("== prefill (causal chunk n against c cached) over an fp8 (e4m3) cache and a 2-byte cache, D=128 ==")
-        for name, Hq, Hkv, n, c in [("yi6b chunk2k@30k", 32, 4, 2048, 30720), ("llama70b/tp8 chunk2k@30k", 8, 1, 2048, 30720), ("yi6b chunk4k@28k", 32, 4, 4096, 28672),
-                                    ("llama8b chunk512@8k", 32, 8, 512, 7680)]:
+        for name, Hq, Hkv, n, c in PF_AB_SHAPES:
             if (ONLY and not any(o.strip() in name for o in ONLY.split(","))) or (not ONLY and "chunk2k@30k" not in name):
                 continue
             fp8_prefill_ab(name, Hq, Hkv, n, c)
@@ -509,8 +625,7 @@ if __name__ == "__main__":
             prefill(v)
     if "decode" in what and "--kv-fp8" in sys.argv:
         print("== decode (Sq=1, append + split-KV + combine) over a 2-byte and an fp8 (e4m3) cache, %s, D=128 ==" % ("bf16" if DTYPE == torch.bfloat16 else "fp16"))
-        for name, Hq, Hkv, B, ctx in [("llama8b B16@32k", 32, 8, 16, 32768), ("llama8b B1@128k", 32, 8, 1, 131072), ("yi6b B16@32k", 32, 4, 16, 32768),
-                                      ("llama8b B64@8k", 32, 8, 64, 8192), ("llama70b/tp8 B64@32k", 8, 1, 64, 32768), ("mqa G32 B16@16k", 32, 1, 16, 16384)]:
+        for name, Hq, Hkv, B, ctx in DC_AB_SHAPES:
             if ONLY and not any(o.strip() in name for o in ONLY.split(",")):
                 continue
             fp8_ab(name, B, 1, Hq, Hkv, ctx, B)

@@ -40,6 +40,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         self.is_profiling_iteration = False
         self._rotary = None
         self._window = None
+        self._softcap = None
         self._num_layers = model_config.get_num_layers(parallel_config)
         self._reset()
 
@@ -48,6 +49,9 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         rotary_embedding.py:75-84) and pass UN-rotated q / k to forward(): RoPE is then applied inside the attention and
         cache-append launches (q and the new k rows in registers, the rotated k lands in the cache) instead of by a separate
         kernel before the wrapper (models/yi.py:172-173).  None switches back to the reference's dataflow."""
+        if cos_sin_cache is not None and self._softcap is not None:
+            raise ValueError("set_fused_rotary: a fused rotary table conflicts with the logit softcap that is set (the softcap kernels do not rotate: "
+                             "rotate q / k before forward(), or set_logit_softcap(None) first)")
         self._rotary = cos_sin_cache
 
     def set_sliding_window(self, left: Optional[int]) -> None:
@@ -60,6 +64,22 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
             raise ValueError("set_sliding_window: left must be >= 0 or None")
         self._window = None if left is None else int(left)
         self._dec_plan = None
+
+    def set_logit_softcap(self, cap: Optional[float]) -> None:
+        """MI355X extension: logit soft-capping for every prefill and decode call of this wrapper — scores = cap * tanh(q.k * softmax_scale /
+        cap), flash_attn's `softcap` (Gemma-2 / Gemma-3: attn_logit_softcapping = 50; their local layers add set_sliding_window).  None or 0
+        (the default) is the reference's dataflow.  With a cap the calls take the default launches, exactly as windowed calls do (no prefill
+        work list, no prefill64).  The softcap kernels do not rotate: a fused rotary table and a cap exclude each other, in either order."""
+        cap = None if cap is None or float(cap) == 0.0 else _FA._softcap_value(cap)
+        if cap is not None and self._rotary is not None:
+            raise ValueError("set_logit_softcap: a logit softcap conflicts with the fused rotary table that is set (the softcap kernels do not "
+                             "rotate: set_fused_rotary(None) and rotate q / k before forward())")
+        self._softcap = cap
+        self._dec_plan = None
+
+    @property
+    def logit_softcap(self) -> Optional[float]:
+        return self._softcap
 
     @property
     def sliding_window(self) -> Optional[int]:
@@ -185,6 +205,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
                                                max(self.prefill_query_lens), self._prefill_totals, self.batch_index[:P],
                                                softmax_scale=softmax_scale, causal=True, out=output[:tok].view(tok, Hq, D),
                                                num_splits=num_splits, _rotary_cos_sin=self._rotary, window_size=self._window_size(),
+                                               softcap=self._softcap or 0.0,
                                                _max_seqlen_k=max(c + n for c, n in zip(self.prefill_cache_lens, self.prefill_query_lens)),
                                                _pf_plan=self._prefill_plan("varlen", self.prefill_query_lens,
                                                                            [c + n for c, n in zip(self.prefill_cache_lens, self.prefill_query_lens)], num_splits))
@@ -211,6 +232,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
                                         causal=True, softmax_scale=softmax_scale,
                                         out=output[tok:tok + q_len].view(1, q_len, Hq, D), _max_seqlen_k=c_len + q_len,
                                         num_splits=num_splits, _rotary_cos_sin=self._rotary, window_size=self._window_size(),
+                                        softcap=self._softcap or 0.0,
                                         _pf_plan=self._prefill_plan(i, [q_len], [c_len + q_len], num_splits) if q_len > 1 else None)
             tok += q_len
         return tok
@@ -219,7 +241,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
         """The work list of one prefill call site of this iteration (flash_attn.prefill_plan: host arithmetic + one small H2D copy),
         built by the first layer that gets here and shared by the others — it depends on the lengths only.  None when the call cannot
         take a list anyway (an explicit split count, or the call is being recorded for the fused prefill || decode launch)."""
-        if num_splits != 0 or _FA._capture_active() or self._window is not None:      # (a windowed call takes the default launch)
+        if num_splits != 0 or _FA._capture_active() or self._window is not None or self._softcap is not None:      # (a windowed or soft-capped call takes the default launch)
             return None
         pl = self._pf_plans.get(key)
         if pl is None and self.head_dim == 128:
@@ -270,7 +292,7 @@ class VAttentionFlashAttentionWrapper(BaseAttentionWrapper):
             tm.work = self._dc_bytes
             flash_attn_with_kvcache(dq, k_all[:, :self.max_cache_len], v_all[:, :self.max_cache_len], dk, dv,
                                     cache_seqlens=self.decode_cache_lens, block_table=None,
-                                    softmax_scale=softmax_scale, causal=True, window_size=self._window_size(),
+                                    softmax_scale=softmax_scale, causal=True, window_size=self._window_size(), softcap=self._softcap or 0.0,
                                     cache_batch_idx=self.batch_index_gen,
                                     out=output[tok:tok + nb].view(nb, 1, Hq, D), _rotary_cos_sin=self._rotary, _params_out=capture)
             # (no host-side lengths: the launch balances a ragged batch from `cache_seqlens` on the device, csrc/decode_body.h)

@@ -44,7 +44,8 @@ UNROLL_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1000000"]
 # is therefore compiled with the resource-usage remarks on, and the build FAILS when any instantiation of a guarded kernel spills.
 NO_SPILL_KERNELS = {"prefill64_kernels.hip": "prefill64",      # prefill64_kernel and its sliding-window build prefill64w_kernel
                      "prefill64p_kernels.hip": "prefill64p_kernel", "decode_kernels.hip": "decode_",
-                     "prefill_kernels.hip": "prefill_fp8_kernel"}      # the builds over an fp8 cache: their widening must fit the 2-byte siblings' register budget
+                     # the builds over an fp8 cache (their widening must fit the 2-byte siblings' register budget) and the soft-capping builds (their tanh likewise)
+                     "prefill_kernels.hip": ("prefill_fp8_kernel", "prefill_softcap_kernel")}
 # ... except: the bf16 build of decode_stream_kernel (d = 128, one head block) that takes the fused-RoPE path at run time — bf16 rotates through fp32,
 # 12 registers more than three workgroups per CU leave; calls without rotation get the build without that path (decode_kernels.hip,
 # launch_decode_stream).  A scratch segment costs ~9 us per launch (profiles/r06_decode_bf16_scratch.txt): no other kernel may grow one unnoticed.
@@ -82,23 +83,25 @@ def _compile(hipcc, flags, src, obj):
     guard = NO_SPILL_KERNELS.get(os.path.basename(src))
     if not guard:
         return _run([hipcc, *flags, "-c", src, "-o", obj])
+    guards = (guard,) if isinstance(guard, str) else tuple(guard)      # every listed name must be seen, and none of them may spill
+    guarded = lambda n: any(g in n for g in guards)
     cmd = [hipcc, *flags, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
     print("[build]", " ".join(cmd), flush=True)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stderr)
         raise subprocess.CalledProcessError(r.returncode, cmd)
-    name, bad, seen = None, [], 0
+    name, bad, seen = None, [], set()
     for line in r.stderr.splitlines():
         if "remark: Function Name:" in line:
             name = line.split("Function Name:")[1].split()[0]
-            seen += guard in name
-        elif name and guard in name and ("ScratchSize" in line or "VGPRs Spill" in line):      # (SGPRs spilled to vector LANES touch no memory)
+            seen.update(g for g in guards if g in name)
+        elif name and guarded(name) and ("ScratchSize" in line or "VGPRs Spill" in line):      # (SGPRs spilled to vector LANES touch no memory)
             value = int(line.split("]:")[-1].split("[")[0].strip() if "ScratchSize" in line else line.split("Spill:")[1].split()[0])
             if value and not any(a in name for a in SPILL_ALLOWED):
                 bad.append("%s: %s" % (name, line.split("remark:")[1].split("[-R")[0].strip()))
-    if not seen:
-        raise RuntimeError("no resource remarks for %s in %s: the spill guard saw nothing" % (guard, src))
+    if len(seen) < len(guards):
+        raise RuntimeError("no resource remarks for %s in %s: the spill guard saw nothing" % (" / ".join(g for g in guards if g not in seen), src))
     if os.path.basename(src) in RESERVED_VGPR:
         _check_reserved_vgpr(hipcc, flags, src, *RESERVED_VGPR[os.path.basename(src)])
     if bad:

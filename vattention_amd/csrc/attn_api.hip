@@ -339,6 +339,24 @@ static const char* fp8kv_prefill_gate_reason(const vattn_attn_params* p) {
     return nullptr;
 }
 
+// Why a block is outside the gate of the soft-capped call (vattn_softcap_attn_with_kvcache, include/vattn_kernels.h) — rule by rule — or NULL when it
+// passes: every form the plain call takes, window or not, minus what has no softcap build
+static const char* softcap_gate_reason(const vattn_attn_params* p) {
+    if (kLab) return "the measurement build has no softcap kernels (use libvattn_amd.so)";
+    if (p->rotary_cos_sin) return "softcap cannot be combined with fused rotary embedding (rotary_cos_sin): rotate q and k first (vattn_rotary_embedding / vattn_cache_flat_rope)";
+    if (p->split_items) return "softcap cannot be combined with split_items (host item plan)";
+    if (p->pf_items || p->pf_num_wg) return "softcap cannot be combined with pf_items / pf_num_wg (prefill work lists run on prefill64, which has no softcap build)";
+    if (((p->variant >> 1) & 7) == 7) return "softcap: explicit tiling 7 is refused — prefill64 has no softcap build (its tile step is scheduled around the uncapped softmax)";
+    if (p->d != 64 && p->d != 128) return "softcap supports head dimensions 64 and 128";
+    return nullptr;
+}
+// softcap is a finite number > 0 (0 delegates before this is asked) ...
+static bool softcap_ok(float softcap) { return softcap > 0.f && softcap <= 3.402823466e+38f; }
+static const char* kSoftcapValue = "softcap must be finite and >= 0 (0: no cap)";
+// ... and large enough for pre = softmax_scale / softcap, which the kernels multiply every score by, to be a finite fp32 number (a denormal cap)
+static bool softcap_pre_ok(const vattn_attn_params* p, float softcap) { return fabsf(p->softmax_scale / softcap) <= 3.402823466e+38f; }
+static const char* kSoftcapPre = "softcap is too small: softmax_scale / softcap overflows fp32";
+
 // The argument rules both calls over an fp8 cache add to validate(): the scales, whole 16-byte chunks of BYTES in the caches, aligned new rows
 static int fp8kv_check_args(const vattn_attn_params* p, const float* k_scale, const float* v_scale) {
     if (!k_scale || !v_scale) return fail(VATTN_K_ERR_INVALID, "an fp8 KV cache needs k_scale and v_scale (device float32[h_k])");
@@ -487,6 +505,52 @@ int vattn_fp8kv_prefill_plan_describe(const vattn_attn_params* p, vattn_plan_des
     memset(out, 0, sizeof *out);
     fp8kv_prefill_describe(p, out);
     out->workspace_bytes = (int64_t)fp8kv_prefill_workspace_bytes(p);
+    return VATTN_K_OK;
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
+}
+
+int vattn_softcap_attn_with_kvcache(const vattn_attn_params* p, float softcap, void* stream) {
+    if (softcap == 0.0f) return vattn_flash_attn_with_kvcache(p, stream);
+    if (!softcap_ok(softcap)) return fail(VATTN_K_ERR_INVALID, kSoftcapValue);
+    if (!abi_ok(p)) return validate(p);
+    if (!softcap_pre_ok(p, softcap)) return fail(VATTN_K_ERR_INVALID, kSoftcapPre);
+    if (const char* why = softcap_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the softcap rule)
+    int rc = validate(p);
+    if (rc) return rc;
+    if (p->k_new && p->seqlen_knew > 0 && !p->cache_seqlens) return fail(VATTN_K_ERR_INVALID, "If key is supplied, seqlens_k must also be passed in");
+#ifndef VATTN_LAB
+    return decode_form(p) ? launch_softcap_decode_form(p, softcap, (hipStream_t)stream) : launch_softcap_prefill_form(p, softcap, (hipStream_t)stream);
+#else
+    return VATTN_K_ERR_UNSUPPORTED;
+#endif
+}
+
+// The soft-capped call runs the plain call's plan for the same block — its prefill form without the prefill64 branch, the rule of the prefill call
+// over an fp8 cache (prefill_kernels.hip, plan_prefill): same planners, same answers, nothing tuned apart.
+size_t vattn_softcap_attn_workspace_bytes(const vattn_attn_params* p, float softcap) {
+    if (softcap == 0.0f) return vattn_attn_workspace_bytes(p);
+    if (!softcap_ok(softcap) || !abi_ok(p) || !softcap_pre_ok(p, softcap) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || softcap_gate_reason(p)) return 0;
+#ifndef VATTN_LAB
+    return decode_form(p) ? decode_workspace_bytes(p) : fp8kv_prefill_workspace_bytes(p);
+#else
+    return 0;
+#endif
+}
+
+int vattn_softcap_attn_plan_describe(const vattn_attn_params* p, float softcap, vattn_plan_desc* out) {
+    if (softcap == 0.0f) return vattn_attn_plan_describe(p, out);
+    if (!softcap_ok(softcap)) return fail(VATTN_K_ERR_INVALID, kSoftcapValue);
+    if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
+    if (!softcap_pre_ok(p, softcap)) return fail(VATTN_K_ERR_INVALID, kSoftcapPre);
+    if (const char* why = softcap_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    if (!out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0) return fail(VATTN_K_ERR_INVALID, "vattn_softcap_attn_plan_describe: bad shape");
+#ifndef VATTN_LAB
+    memset(out, 0, sizeof *out);
+    if (decode_form(p)) decode_describe(p, out);
+    else fp8kv_prefill_describe(p, out);
+    out->workspace_bytes = (int64_t)vattn_softcap_attn_workspace_bytes(p, softcap);
     return VATTN_K_OK;
 #else
     return VATTN_K_ERR_UNSUPPORTED;

@@ -143,6 +143,17 @@ template <typename T> __device__ __forceinline__ void fp8_widen16(const uint4 x,
     hi = make_uint4(r[4], r[5], r[6], r[7]);
 }
 
+// ---- logit soft-capping: pieces shared by the builds that cap (decode_body.h, prefill_body.h: SOFTCAP) ----
+// scores = cap * tanh(q.k * softmax_scale / cap) (include/vattn_kernels.h, "Logit soft-capping").  The two constants are a kernel argument of
+// those builds alone (vattn_attn_params is frozen): pre = softmax_scale / cap, formed by the host in fp32, and cap itself, which takes the
+// place of softmax_scale in everything behind the tanh (sc = cap * log2e, the LSE).
+struct softcap_arg { float pre; float cap; };
+// tanh(x) = 1 - 2 / (1 + exp2(2 log2e x)) on the hardware exp and reciprocal: branch-free, and its limits come out right without a select
+// (x -> +inf: exp2 = inf, rcp = 0, 1; x -> -inf: exp2 = 0, rcp(1) = 1, -1; NaN stays NaN).  The caller passes x2 = 2 log2e x — for a raw
+// score s that is s * k2 with k2 = pre * 2 log2e formed once per kernel, one multiply per score instead of two.
+__device__ __forceinline__ float tanh_exp2(float x2) { return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + fast_exp2(x2)), 1.f); }
+__device__ __forceinline__ float softcap_k2(const softcap_arg c) { return c.pre * (2.f * kLog2e); }
+
 // ---- rotary position embedding, NeoX pairing (element i with element i + rot_dim/2), on 8-element fragments ----
 // Arithmetic of /root/reference/sarathi-lean/csrc/pos_encoding_kernels.cu:32-35 in `scalar_t`: x' = x*cos - y*sin, y' = y*cos + x*sin
 // with every product and the sum rounded to the I/O dtype (restated by oracle/attn.py rotary_embedding_ref; bit-exact).
@@ -315,6 +326,10 @@ int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipS
 int launch_fp8kv_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st);   // decode_kernels.hip (product library only): decode_form(p) over an e4m3 cache
 // decode_kernels.hip (product library only): the tree-masked multi-token form over an e4m3 cache
 int launch_fp8kv_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale, hipStream_t st);
+// product library only: the softcap builds (vattn_softcap_attn_with_kvcache; cap > 0, finite) — decode_kernels.hip: decode_form(p); prefill_kernels.hip:
+// the prefill form, on the plan without prefill64 that fp8kv_prefill_describe / fp8kv_prefill_workspace_bytes answer
+int launch_softcap_decode_form(const vattn_attn_params* p, float softcap, hipStream_t st);
+int launch_softcap_prefill_form(const vattn_attn_params* p, float softcap, hipStream_t st);
 size_t decode_workspace_bytes(const vattn_attn_params* p);
 int decode_plan(const vattn_attn_params* p, const int32_t* lens, vattn_decode_item* items, int cap, int32_t* seq);   // decode_kernels.hip
 void prefill_describe(const vattn_attn_params* p, vattn_plan_desc* out);   // prefill_kernels.hip

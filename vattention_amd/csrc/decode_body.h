@@ -54,21 +54,30 @@ constexpr int DC_BN = 32;     // keys per wave tile
 // TREE && FP8: the tree-masked multi-token form over an e4m3 cache (vattn_fp8kv_tree_attn_with_kvcache) — the product of the two: the mask only
 // touches the scores of the masked tail tiles, the cache dtype only how K / V bytes become MFMA operands and the two fp32 constants.  Builds of
 // their own again; their last argument carries both the mask words and the scales (fp8_tree_arg), the other builds keep their argument lists.
+// SOFTCAP: logit soft-capping, scores = cap * tanh(q.k * softmax_scale / cap) (vattn_softcap_attn_with_kvcache, include/vattn_kernels.h; one-token and
+// MT builds, with or without WIN, never beside TREE / FP8 / ROPE) — builds of their own, the others carry no trace of it.  t = tanh(s * pre) is taken
+// on the fp32 accumulator BEFORE any mask (a masked score must stay -inf: tanh(-inf) = -1 would unmask it; rows a buffer load zero-filled give
+// tanh(0) = 0 and are masked right after); everything behind it — running max, alpha, the cross-wave merge, published partials, the LSE — is the
+// uncapped code with cap in the place of softmax_scale.  Partials are fp32 in the log2 domain as ever: the merges do not know about the cap.  The
+// two constants are a kernel argument of these builds alone (softcap_arg, attn_common.h), in the place of the TREE builds' mask.
 struct no_tree_mask {};
 struct fp8_tree_arg { const uint32_t* mask; fp8_scales scales; };
-template <bool TREE, bool FP8 = false> using tree_mask_arg = std::conditional_t<TREE, std::conditional_t<FP8, fp8_tree_arg, const uint32_t*>, std::conditional_t<FP8, fp8_scales, no_tree_mask>>;
-// the mask words and the scales out of the last kernel argument of a build (null / empty where the build has none)
-template <bool TREE, bool FP8> __device__ __forceinline__ void unpack_mask_arg(const tree_mask_arg<TREE, FP8>& a, const uint32_t*& tmask, fp8_scales& scales) {
-    if constexpr (TREE && FP8) { tmask = a.mask; scales = a.scales; }
+template <bool TREE, bool FP8 = false, bool SOFTCAP = false> using tree_mask_arg =
+    std::conditional_t<SOFTCAP, softcap_arg, std::conditional_t<TREE, std::conditional_t<FP8, fp8_tree_arg, const uint32_t*>, std::conditional_t<FP8, fp8_scales, no_tree_mask>>>;
+// the mask words, the scales and the cap out of the last kernel argument of a build (null / empty where the build has none)
+template <bool TREE, bool FP8, bool SOFTCAP = false> __device__ __forceinline__ void unpack_mask_arg(const tree_mask_arg<TREE, FP8, SOFTCAP>& a, const uint32_t*& tmask, fp8_scales& scales, softcap_arg& cap) {
+    if constexpr (SOFTCAP) cap = a;
+    else if constexpr (TREE && FP8) { tmask = a.mask; scales = a.scales; }
     else if constexpr (TREE) tmask = a;
     else if constexpr (FP8) scales = a;
 }
-template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
+template <typename T, int HD, bool USE_TR, int NB = 1, int W = DC_WAVES, int PF = 1, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false, bool SOFTCAP = false>
 __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const int num_splits, const int gblocks, const int fused_append,
                                             const int split, const int hk, const int gb, const int b, char* smem,
                                             const int item = -1, const int item_tb = 0, const int item_te = 0,
                                             const int st_mode = 0, const int st_slot = 0, const int st_lk = 0, const unsigned st_block = 0,
-                                            const int tstride = 1, const uint32_t* tree_mask = nullptr, const fp8_scales scales = {}) {
+                                            const int tstride = 1, const uint32_t* tree_mask = nullptr, const fp8_scales scales = {}, const softcap_arg cap = {}) {
+    static_assert(!SOFTCAP || (!TREE && !FP8 && ROPE == 0 && W == DC_WAVES && USE_TR), "the softcap builds: one-token and multi-token, with or without a window; no tree mask, fp8 cache or rotation");
     static_assert(!TREE || (MT && !WIN), "the tree mask belongs to the window-less multi-token builds");
     static_assert(!FP8 || (!WIN && ROPE == 0 && W == DC_WAVES && USE_TR), "the fp8 cache builds: one-token, multi-token and tree-masked multi-token, no window / rotation");
     // st_mode != 0: a piece [item_tb, item_te) of the device-planned stream decomposition (decode_stream_kernel below).  Slot and visible
@@ -190,7 +199,9 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
     }
     float sm_scale = p.softmax_scale;                    // FP8: k_scale[hk] folded in (scores = q . stored * k_scale)
     if constexpr (FP8) sm_scale *= scales.k[hk];
+    if constexpr (SOFTCAP) sm_scale = cap.cap;           // SOFTCAP: the softmax runs on t = tanh(s * pre) with the cap as its scale
     const float sc = sm_scale * kLog2e;
+    [[maybe_unused]] const float cap_k2 = softcap_k2(cap);      // (SOFTCAP only)
     char* vsm = smem + wave * V_WAVE_BYTES;
 
     uint4 kreg[PF][2][KL], vreg[PF][VPASS];
@@ -327,6 +338,12 @@ __device__ __forceinline__ void decode_body(const vattn_attn_params& p, const in
         V8 pf[NB];
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) {
+            if constexpr (SOFTCAP) {      // before any mask (see SOFTCAP above)
+#pragma unroll
+                for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) s[nb][kb][r] = tanh_exp2(s[nb][kb][r] * cap_k2);
+            }
             if (RAGGED && !MT) {
 #pragma unroll
                 for (int kb = 0; kb < 2; kb++)
@@ -808,11 +825,12 @@ __device__ __forceinline__ void decode_stream_merge(const vattn_attn_params& p, 
 
 // nwg: workgroups per (kv head, group) = gridDim.x.  The partials are merged by decode_stream_combine_kernel in a second launch (merging
 // inside the launch, XCD-consecutive ranges, per-workgroup clock stamps, fair-share issue priority: tools/lab/csrc/decode_body_lab.h).
-template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
-__global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append, tree_mask_arg<TREE, FP8> tree_mask = {}) {
+template <typename T, int HD, bool USE_TR, int NB, int ROPE = -1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false, bool SOFTCAP = false>
+__global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_kernel(vattn_attn_params p, int gblocks, int fused_append, tree_mask_arg<TREE, FP8, SOFTCAP> tree_mask = {}) {
     const uint32_t* tmask = nullptr;
     fp8_scales scales = {};
-    unpack_mask_arg<TREE, FP8>(tree_mask, tmask, scales);
+    softcap_arg cap = {};
+    unpack_mask_arg<TREE, FP8, SOFTCAP>(tree_mask, tmask, scales, cap);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_plan[3 * DC_MAXB];                // stream mode: the plan, for the pieces after the first
     const int tid = threadIdx.x;
@@ -881,7 +899,7 @@ __global__ __launch_bounds__(64 * DC_WAVES, NB > 1 ? 2 : 3) void decode_stream_k
     for (;;) {
         const unsigned blk = stream_table_bytes(p.b) + (((unsigned)(w + b) * p.h_k + hk) * gblocks + gb) * RB;
         if (tb == 0 && hk == 0 && gb == 0 && tid == 0) stream_publish_seq(p, b, first_rec, cnt);      // (the owner of the sequence's first piece)
-        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT, TREE, FP8>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk, 1, tmask, scales);
+        decode_body<T, HD, USE_TR, NB, DC_WAVES, 1, ROPE, WIN, MT, TREE, FP8, SOFTCAP>(p, 2, gblocks, fused_append, 0, hk, gb, b, smem, 0, tb, te, cnt == 1 ? 1 : 2, slot, lk, blk, 1, tmask, scales, cap);
         if (geo.uniform || !next_piece(b + 1)) return;
         __syncthreads();                                 // the previous piece's in-workgroup merge is done with the LDS
     }
@@ -900,14 +918,15 @@ __global__ __launch_bounds__(256) void decode_stream_combine_kernel(vattn_attn_p
 
 // gblocks = head-block GROUPS per kv head (ceil(ceil(G/16) / NB)).  The partials of a split launch are merged by combine_kernel in a
 // second launch (the single-launch merges live in the lab copy).
-template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false>
-__global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append, tree_mask_arg<TREE, FP8> tree_mask = {}) {
+template <typename T, int HD, bool USE_TR, int NB, int W = DC_WAVES, int PF = 1, bool WIN = false, bool MT = false, bool TREE = false, bool FP8 = false, bool SOFTCAP = false>
+__global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB > 1) || PF > 1) ? 2 : 3) void decode_kernel(vattn_attn_params p, int num_splits, int gblocks, int fused_append, tree_mask_arg<TREE, FP8, SOFTCAP> tree_mask = {}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const uint32_t* tmask = nullptr;
     fp8_scales scales = {};
-    unpack_mask_arg<TREE, FP8>(tree_mask, tmask, scales);
+    softcap_arg cap = {};
+    unpack_mask_arg<TREE, FP8, SOFTCAP>(tree_mask, tmask, scales, cap);
     int split, hk, gb, b;
-    if (!MT && !FP8 && p.split_items != nullptr) {          // (host items: the one-token form only, 2-byte caches only)
+    if (!MT && !FP8 && !SOFTCAP && p.split_items != nullptr) {          // (host items: the one-token form only, 2-byte caches only, no cap)
         // length-balanced plan: blockIdx.x = work item (a piece of ONE sequence), blockIdx.y = (kv head, head-block group)
         const vattn_decode_item it = p.split_items[blockIdx.x];
         decode_body<T, HD, USE_TR, NB, W, PF, -1, WIN>(p, 2, gblocks, fused_append, it.index_in_seq, blockIdx.y / gblocks, blockIdx.y % gblocks, it.b, smem,
@@ -933,8 +952,8 @@ __global__ __launch_bounds__(64 * W, W > 4 ? 4 : (HD > 128 || (HD == 128 && NB >
         gb = blockIdx.y % gblocks;
         b = blockIdx.z;
     }
-    decode_body<T, HD, USE_TR, NB, W, PF, (MT || FP8) ? 0 : -1, WIN, MT, TREE, FP8>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
-                                          (decode_striped(p) && num_splits > 1) ? num_splits : 1, tmask, scales);
+    decode_body<T, HD, USE_TR, NB, W, PF, (MT || FP8 || SOFTCAP) ? 0 : -1, WIN, MT, TREE, FP8, SOFTCAP>(p, num_splits, gblocks, fused_append, split, hk, gb, b, smem, -1, 0, 0, 0, 0, 0, 0,
+                                          (decode_striped(p) && num_splits > 1) ? num_splits : 1, tmask, scales, cap);
 }
 
 }  // namespace vattn_k

@@ -209,10 +209,11 @@ static size_t stream_workspace_bytes(const vattn_attn_params* p, int nwg) {
 // form), else by a separate append launch in front of it on the same stream (seqlen_knew > 1; the multi-token form, which has no fused
 // rotation either).
 // What travels BESIDE the parameter block (vattn_attn_params is frozen): the mask words of the tree-masked call, the per-kv-head scales of a
-// call over an fp8 cache (decode_body.h: TREE, FP8)
-struct decode_extra { const uint32_t* tree_mask; const float* k_scale; const float* v_scale; };
+// call over an fp8 cache, the two constants of a soft-capped call (decode_body.h: TREE, FP8, SOFTCAP)
+struct decode_extra { const uint32_t* tree_mask; const float* k_scale; const float* v_scale; softcap_arg cap; };
 struct decode_launch { size_t smem; int fused_append; };
 // FP8: no fused append — the new rows are quantised by the append launch (cache_kernels.hip, launch_append_fp8), whatever their count
+// (a soft-capped call appends as the plain call does: ONE new row in the attention kernel, more by the append launch)
 template <int HD, bool MT, bool FP8> static decode_launch begin_decode_launch(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
     const int fused_append = (!MT && !FP8 && p->k_new && p->seqlen_knew == 1) ? 1 : 0;
     if (p->k_new && !fused_append) {
@@ -222,9 +223,10 @@ template <int HD, bool MT, bool FP8> static decode_launch begin_decode_launch(co
     return {(size_t)DC_WAVES * 16 * HD * 4 + DC_WAVES * 16 * 4 * 2, fused_append};
 }
 // The last kernel argument of every build: the mask words of the TREE builds, the scale pointers of the FP8 builds, both for the TREE && FP8
-// builds, an empty struct for the others (decode_body.h, tree_mask_arg)
-template <bool TREE, bool FP8> static tree_mask_arg<TREE, FP8> mask_arg(const decode_extra& x) {
-    if constexpr (TREE && FP8) return fp8_tree_arg{x.tree_mask, fp8_scales{x.k_scale, x.v_scale}};
+// builds, the cap's two constants for the SOFTCAP builds, an empty struct for the others (decode_body.h, tree_mask_arg)
+template <bool TREE, bool FP8, bool CAP = false> static tree_mask_arg<TREE, FP8, CAP> mask_arg(const decode_extra& x) {
+    if constexpr (CAP) return x.cap;
+    else if constexpr (TREE && FP8) return fp8_tree_arg{x.tree_mask, fp8_scales{x.k_scale, x.v_scale}};
     else if constexpr (TREE) return x.tree_mask;
     else if constexpr (FP8) return fp8_scales{x.k_scale, x.v_scale};
     else return {};
@@ -234,26 +236,27 @@ template <bool TREE, bool FP8> static tree_mask_arg<TREE, FP8> mask_arg(const de
 // MT: the multi-token builds — no fused append, no fused rotation (ROPE 0)
 // TREE: the tree-masked builds of the multi-token form (decode_body.h) — the same plan, grid and workspace; the mask is their extra argument
 // FP8: the builds that read an e4m3 cache (decode_body.h) — the same plan, grid, workspace and merges; the scales are their extra argument
-template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const decode_extra& x) {
+// CAP: the soft-capping builds (decode_body.h, SOFTCAP) — the same plan, grid, workspace and merges; pre and the cap are their extra argument
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8, bool CAP = false> int launch_decode_stream(const vattn_attn_params* p, hipStream_t st, int nwg, const decode_extra& x) {
     if (!p->workspace) return fail(VATTN_K_ERR_INVALID, "split-KV decode needs a workspace");
     if (stream_workspace_bytes(p, nwg) >= 0x7fffffffull) return fail(VATTN_K_ERR_UNSUPPORTED, "decode batch too large for the 32-bit record offsets");
     const decode_launch l = begin_decode_launch<HD, MT, FP8>(p, st, x);
     const dim3 grid((unsigned)nwg, (unsigned)p->h_k), block(64 * DC_WAVES);
-    auto kernel = decode_stream_kernel<T, HD, true, NB, (MT || FP8) ? 0 : -1, WIN, MT, TREE, FP8>;
-    if constexpr (!MT && !FP8 && __is_same(T, __bf16)) {
+    auto kernel = decode_stream_kernel<T, HD, true, NB, (MT || FP8 || CAP) ? 0 : -1, WIN, MT, TREE, FP8, CAP>;
+    if constexpr (!MT && !FP8 && !CAP && __is_same(T, __bf16)) {
         // bf16 rotates through fp32 (no packed arithmetic): with the fused-RoPE path compiled in, decode_stream_kernel<bf16, 128, one head block> is
         // 12 registers over the 168 of three workgroups per CU and gets a scratch segment — 9 us per launch even when no rotation is asked for
         // (profiles/r06_decode_bf16_scratch.txt).  Two builds: without the path (what the reference's wrapper calls: no spill), and the one that
         // takes it at run time (the path compiled in UNCONDITIONALLY spills more: 46 registers instead of 12).
         if (!p->rotary_cos_sin) kernel = decode_stream_kernel<T, HD, true, NB, 0, WIN, MT, TREE, FP8>;
     }
-    hipLaunchKernelGGL(kernel, grid, block, l.smem, st, *p, 1, l.fused_append, mask_arg<TREE, FP8>(x));
+    hipLaunchKernelGGL(kernel, grid, block, l.smem, st, *p, 1, l.fused_append, mask_arg<TREE, FP8, CAP>(x));
     hipLaunchKernelGGL((decode_stream_combine_kernel<T, HD, NB, MT>), dim3((unsigned)p->b, (unsigned)p->h_k), dim3(256), 0, st, *p, 1);
     return launch_status();
 }
 
-template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
-    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT, TREE, FP8>(p, st, nwg, x);
+template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8, bool CAP = false> int launch_decode_nb(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    if (const int nwg = stream_nwg(p)) return launch_decode_stream<T, HD, NB, WIN, MT, TREE, FP8, CAP>(p, st, nwg, x);
     const int groups = decode_groups(p);
     const bool planned = p->split_items != nullptr;
     if (planned && (!p->split_seq || p->num_split_items <= 0)) return fail(VATTN_K_ERR_INVALID, "split_items needs split_seq and num_split_items");
@@ -266,7 +269,7 @@ template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> in
         grid = dim3((unsigned)(((w + 7) / 8) * 8 * groups));
     }
     const decode_launch l = begin_decode_launch<HD, MT, FP8>(p, st, x);
-    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT, TREE, FP8>), grid, block, l.smem, st, *p, splits, groups, l.fused_append, mask_arg<TREE, FP8>(x));
+    hipLaunchKernelGGL((decode_kernel<T, HD, true, NB, DC_WAVES, 1, WIN, MT, TREE, FP8, CAP>), grid, block, l.smem, st, *p, splits, groups, l.fused_append, mask_arg<TREE, FP8, CAP>(x));
     const int sq = MT ? p->seqlen_q : 1;
     if (planned) hipLaunchKernelGGL((combine_items_kernel<T, HD>), dim3(p->b * p->h), dim3(128), 0, st, *p);
     else if (splits > 1) hipLaunchKernelGGL((combine_kernel<T, HD>), dim3(p->b * sq * p->h), dim3(128), 0, st, *p, splits, sq);
@@ -278,10 +281,17 @@ template <typename T, int HD, int NB, bool WIN, bool MT, bool TREE, bool FP8> in
 // multi-token form (the caller checked multitoken_form(p)), with or without a window; then one or two head blocks per workgroup.  FP8
 // (vattn_fp8kv_attn_with_kvcache: the caller checked its gate — decode_form(p), no window): one token or the multi-token form on the FP8 builds.
 // TREE && FP8 (vattn_fp8kv_tree_attn_with_kvcache: the caller checked both gates): the TREE launch on the builds that carry both switches.
-template <typename T, int HD, bool WIN, bool MT, bool TREE, bool FP8> int launch_decode_w(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
-    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, WIN, MT, TREE, FP8>(p, st, x) : launch_decode_nb<T, HD, 1, WIN, MT, TREE, FP8>(p, st, x);
+// CAP (vattn_softcap_attn_with_kvcache: the caller checked its gate — decode_form(p), no host items, no rotation): what the plain call takes — one
+// token or the multi-token form, with or without a window — on the SOFTCAP builds.
+template <typename T, int HD, bool WIN, bool MT, bool TREE, bool FP8, bool CAP = false> int launch_decode_w(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    return decode_nb(p) == 2 ? launch_decode_nb<T, HD, 2, WIN, MT, TREE, FP8, CAP>(p, st, x) : launch_decode_nb<T, HD, 1, WIN, MT, TREE, FP8, CAP>(p, st, x);
 }
-template <typename T, int HD, bool TREE, bool FP8> int launch_decode_t(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+template <typename T, int HD, bool TREE, bool FP8, bool CAP = false> int launch_decode_t(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+    if constexpr (CAP) {
+        const bool win = p->window_left_plus1 > 0;
+        if (p->seqlen_q == 1) return win ? launch_decode_w<T, HD, true, false, false, false, true>(p, st, x) : launch_decode_w<T, HD, false, false, false, false, true>(p, st, x);
+        return win ? launch_decode_w<T, HD, true, true, false, false, true>(p, st, x) : launch_decode_w<T, HD, false, true, false, false, true>(p, st, x);
+    } else
     if constexpr (TREE) return launch_decode_w<T, HD, false, true, true, FP8>(p, st, x);
     else if constexpr (FP8) return p->seqlen_q == 1 ? launch_decode_w<T, HD, false, false, false, true>(p, st, x) : launch_decode_w<T, HD, false, true, false, true>(p, st, x);
     else {
@@ -290,19 +300,23 @@ template <typename T, int HD, bool TREE, bool FP8> int launch_decode_t(const vat
         return win ? launch_decode_w<T, HD, true, true, false, false>(p, st, x) : launch_decode_w<T, HD, false, true, false, false>(p, st, x);
     }
 }
-// dtype x head dimension: the one ladder of the four entry points
-template <bool TREE, bool FP8> static int launch_decode_dtype_hd(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
+// dtype x head dimension: the one ladder of the five entry points
+template <bool TREE, bool FP8, bool CAP = false> static int launch_decode_dtype_hd(const vattn_attn_params* p, hipStream_t st, const decode_extra& x) {
     const bool f16 = p->dtype == VATTN_DTYPE_F16;
-    if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64, TREE, FP8>(p, st, x) : launch_decode_t<__bf16, 64, TREE, FP8>(p, st, x);
-    return f16 ? launch_decode_t<_Float16, 128, TREE, FP8>(p, st, x) : launch_decode_t<__bf16, 128, TREE, FP8>(p, st, x);
+    if (p->d == 64) return f16 ? launch_decode_t<_Float16, 64, TREE, FP8, CAP>(p, st, x) : launch_decode_t<__bf16, 64, TREE, FP8, CAP>(p, st, x);
+    return f16 ? launch_decode_t<_Float16, 128, TREE, FP8, CAP>(p, st, x) : launch_decode_t<__bf16, 128, TREE, FP8, CAP>(p, st, x);
 }
-int launch_decode_form(const vattn_attn_params* p, hipStream_t st) { return launch_decode_dtype_hd<false, false>(p, st, {nullptr, nullptr, nullptr}); }
-int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) { return launch_decode_dtype_hd<true, false>(p, st, {tree_mask, nullptr, nullptr}); }
+int launch_decode_form(const vattn_attn_params* p, hipStream_t st) { return launch_decode_dtype_hd<false, false>(p, st, {nullptr, nullptr, nullptr, {}}); }
+int launch_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, hipStream_t st) { return launch_decode_dtype_hd<true, false>(p, st, {tree_mask, nullptr, nullptr, {}}); }
 int launch_fp8kv_form(const vattn_attn_params* p, const float* k_scale, const float* v_scale, hipStream_t st) {
-    return launch_decode_dtype_hd<false, true>(p, st, {nullptr, k_scale, v_scale});
+    return launch_decode_dtype_hd<false, true>(p, st, {nullptr, k_scale, v_scale, {}});
 }
 int launch_fp8kv_tree_form(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale, hipStream_t st) {
-    return launch_decode_dtype_hd<true, true>(p, st, {tree_mask, k_scale, v_scale});
+    return launch_decode_dtype_hd<true, true>(p, st, {tree_mask, k_scale, v_scale, {}});
+}
+// pre = softmax_scale / softcap in fp32, on the host (include/vattn_kernels.h, "Logit soft-capping")
+int launch_softcap_decode_form(const vattn_attn_params* p, float softcap, hipStream_t st) {
+    return launch_decode_dtype_hd<false, false, true>(p, st, {nullptr, nullptr, nullptr, {p->softmax_scale / softcap, softcap}});
 }
 
 // Length-balanced split of a ragged decode batch (include/vattn_kernels.h, vattn_decode_plan).  Every sequence is cut into pieces of at

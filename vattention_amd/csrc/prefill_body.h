@@ -23,10 +23,16 @@ namespace vattn_k {
 // half the loads per tile, each widened in registers (exact) into the TWO 16-byte chunks of T the 2-byte build would have stored — the LDS image is
 // that build's for the unscaled values, and everything that reads LDS is unchanged.  The scales never touch an element: k_scale[hk] folds into sc
 // (and the LSE), v_scale[hk] into the final 1 / l, so partials are published scaled and combine_rows_kernel does not know the cache dtype.
-template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM, bool WIN = false, bool FP8 = false>
+// SOFTCAP: logit soft-capping, scores = cap * tanh(q.k * softmax_scale / cap) (vattn_softcap_attn_with_kvcache, include/vattn_kernels.h) — builds of
+// their own (prefill_softcap_kernel below), with or without WIN, never beside FP8 or a rotary table; the others carry no trace of it: the tile step is
+// bound by what a wave can issue to the vector ALU, and the cap is two more transcendentals per score.  t = tanh(s * pre) is taken on the fp32
+// accumulator in front of need_mask (a masked score must stay -inf: tanh(-inf) = -1 would unmask it); behind it the cap stands where softmax_scale
+// stood: sc, alpha, the published partials (log2 domain: combine_rows_kernel does not know about the cap) and the LSE.
+template <typename T, int HD, bool USE_TR, int WAVES, int QC, bool MSUM, bool WIN = false, bool FP8 = false, bool SOFTCAP = false>
 __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const int b, const int h, const int qb, const int split, const int nsplit, char* smem,
-                                             const fp8_scales scales = {}) {
+                                             const fp8_scales scales = {}, const softcap_arg cap = {}) {
     static_assert(!FP8 || (!WIN && !MSUM && QC == 1 && USE_TR), "the fp8 cache builds: 32-row waves, no window");
+    static_assert(!SOFTCAP || (!FP8 && !MSUM && QC == 1 && USE_TR), "the softcap builds: 32-row waves, with or without a window, 2-byte caches");
     using X = Tr<T>;
     using V8 = typename X::v8;
     using S = PfSmem<HD>;
@@ -91,7 +97,7 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
             if (my_q < Sq) v = *(const uint4*)(qptr + 16 * kk + 8 * g);
             qf[qc][kk] = as_v8<V8>(v);
         }
-        if (p.rotary_cos_sin && my_q < Sq && off + my_q >= 0) {
+        if (!SOFTCAP && p.rotary_cos_sin && my_q < Sq && off + my_q >= 0) {      // (the softcap gate refuses a rotary table: ROPE is compiled out there)
             // fused RoPE: query row i sits at position (visible keys - Sq) + i; slot (g, j) of k-step kk is element 16*kk + 8*g + j,
             // so an element and its partner d + HD/2 live in the same lane (k-steps kk and kk + KK/2).  A row in front of position 0
             // (Sq > Lk) has no table row: it stays un-rotated and none is read (include/vattn_kernels.h; causal / windowed: it sees no
@@ -131,7 +137,9 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
     }
     float sm_scale = p.softmax_scale;                    // FP8: k_scale[hk] folded in (scores = q . stored * k_scale)
     if constexpr (FP8) sm_scale *= scales.k[hk];
+    if constexpr (SOFTCAP) sm_scale = cap.cap;           // SOFTCAP: the softmax runs on t = tanh(s * pre) with the cap as its scale
     const float sc = sm_scale * kLog2e;
+    [[maybe_unused]] const float cap_k2 = softcap_k2(cap);      // (SOFTCAP only)
 
     // two register sets: the loads of tile t+2 are issued while tile t is computed and are only consumed (stored to
     // LDS) at the end of iteration t+1 -> a two-iteration latency budget instead of one (L2/MALL latency under load
@@ -250,6 +258,14 @@ __device__ __forceinline__ void prefill_body(const vattn_attn_params& p, const i
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 2 * QC, 0);
             // s[kb][qc][r] = S^T[key = n0 + 32*kb + 8*(r>>2) + 4*g + (r&3)][query = qw0 + 32*qc + l31]
+            if constexpr (SOFTCAP) {      // before any mask (see SOFTCAP above)
+#pragma unroll
+                for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+                    for (int qc = 0; qc < QC; qc++)
+#pragma unroll
+                        for (int r = 0; r < 16; r++) s[kb][qc][r] = tanh_exp2(s[kb][qc][r] * cap_k2);
+            }
             const bool need_mask = (n0 + PF_BN > Lk) || (causal && (n0 + PF_BN - 1 > qw0 + off)) || (WIN && (n0 < qw0 + 32 * QC - 1 + off - left));
             float alpha[QC];
 #pragma unroll
@@ -432,6 +448,16 @@ __global__ __launch_bounds__(64 * WAVES, 2) void prefill_fp8_kernel(vattn_attn_p
     int b, h, qb, split;
     if (!wg_to_work(p, order, nqb, nsplit, b, h, qb, split)) return;
     prefill_body<T, HD, true, WAVES, 1, false, false, true>(p, b, h, qb, split, nsplit, smem, scales);
+}
+
+// The SOFTCAP builds' kernel: prefill_kernel's mapping, pre and the cap as the extra argument (32-row waves, with or without a window; launch bounds of
+// the uncapped sibling)
+template <typename T, int HD, int WAVES, bool WIN>
+__global__ __launch_bounds__(64 * WAVES, 2) void prefill_softcap_kernel(vattn_attn_params p, int order, int nqb, int nsplit, softcap_arg cap) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int b, h, qb, split;
+    if (!wg_to_work(p, order, nqb, nsplit, b, h, qb, split)) return;
+    prefill_body<T, HD, true, WAVES, 1, false, WIN, false, true>(p, b, h, qb, split, nsplit, smem, {}, cap);
 }
 
 }  // namespace vattn_k

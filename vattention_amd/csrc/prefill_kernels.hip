@@ -6,6 +6,8 @@
 //                         optional KV split (fp32 partials merged by combine_rows_kernel) and batched variable-length chunks
 //   prefill_fp8_kernel  : prefill_kernel's body over an fp8 (e4m3) cache (prefill_body.h, FP8): the bytes are widened on their way into LDS,
 //                         the per-head scales fold into the softmax scale and the final 1 / l (vattn_fp8kv_prefill_with_kvcache)
+//   prefill_softcap_kernel : prefill_kernel's body with logit soft-capping (prefill_body.h, SOFTCAP): tanh on the fp32 scores in front of the
+//                         masks, the cap in the place of the softmax scale behind it (vattn_softcap_attn_with_kvcache)
 //   prefill_ilv_kernel  : the same data flow software-pipelined with a hand-written issue order (variant 12)
 // Semantics: /root/reference/pod_attn/pod_attn/flash_attn_interface.py:1146-1291, flash_api.cpp:1291-1578, mask.h:164-196
 // (bottom-right causal), softmax.h:69-157 (fp32 max/sum, exp2, P rounded to the I/O dtype before PV).
@@ -139,7 +141,7 @@ dim3 prefill_grid(const vattn_attn_params* p, int nqb, int nsplit, int* order_ou
 //  nsplit  > 1 when the grid would leave CUs idle (tensor-parallel shards with few heads, short chunks): every work item's
 //          key range is divided over nsplit workgroups, fp32 partials go through the workspace, combine_kernel merges them.
 //  with_p64 = false: the plan of a call that has no prefill64 build (an fp8 cache: prefill64 moves its tiles by LDS-DMA and cannot widen them in
-//          flight) — the same rules with the prefill64 branch skipped, so tiling 1 or 4 and the split count those rules give; nothing tuned apart.
+//          flight; a soft-capped call: its tile step is hand-scheduled around the uncapped softmax) — the same rules with the prefill64 branch skipped, so tiling 1 or 4 and the split count those rules give; nothing tuned apart.
 struct PrefillPlan { int tiling; int nsplit; };
 PrefillPlan plan_prefill(const vattn_attn_params* p, const bool with_p64 = true) {
     PrefillPlan pl;
@@ -258,7 +260,8 @@ static void launch_combine_rows(void (*kernel)(vattn_attn_params, int, int, int6
 
 // (the single-launch merge of the key-range shares — variant bits 14 / 15 — measured slower and lives in the lab copy: profiles/r02_kbench_prefill_merge.txt)
 // FP8: the builds over an e4m3 cache (prefill_fp8_kernel) — the same grid, order, LDS and merge; the scales are their extra argument
-template <typename T, int HD, int WAVES, int QC, bool WIN = false, bool FP8 = false> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit, const fp8_scales sc) {
+// CAP: the soft-capping builds (prefill_softcap_kernel) — the same grid, order, LDS and merge; pre and the cap are their extra argument
+template <typename T, int HD, int WAVES, int QC, bool WIN = false, bool FP8 = false, bool CAP = false> void launch_prefill(const vattn_attn_params* p, hipStream_t st, int nsplit, const fp8_scales sc, const softcap_arg cap = {}) {
     constexpr bool MSUM = false;
     constexpr int BM = 32 * QC * WAVES;
     const int nqb = (p->seqlen_q + BM - 1) / BM;
@@ -267,12 +270,14 @@ template <typename T, int HD, int WAVES, int QC, bool WIN = false, bool FP8 = fa
     const dim3 block(64 * WAVES);
     const size_t smem = PfSmem<HD>::kTotal;
     static const bool attr_once = [] {   // 64 KiB of dynamic LDS per workgroup
-        if constexpr (FP8) (void)hipFuncSetAttribute((const void*)prefill_fp8_kernel<T, HD, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
+        if constexpr (CAP) (void)hipFuncSetAttribute((const void*)prefill_softcap_kernel<T, HD, WAVES, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
+        else if constexpr (FP8) (void)hipFuncSetAttribute((const void*)prefill_fp8_kernel<T, HD, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
         else (void)hipFuncSetAttribute((const void*)prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, PfSmem<HD>::kTotal);
         return true;
     }();
     (void)attr_once;
-    if constexpr (FP8) hipLaunchKernelGGL((prefill_fp8_kernel<T, HD, WAVES>), grid, block, smem, st, *p, order, nqb, nsplit, sc);
+    if constexpr (CAP) hipLaunchKernelGGL((prefill_softcap_kernel<T, HD, WAVES, WIN>), grid, block, smem, st, *p, order, nqb, nsplit, cap);
+    else if constexpr (FP8) hipLaunchKernelGGL((prefill_fp8_kernel<T, HD, WAVES>), grid, block, smem, st, *p, order, nqb, nsplit, sc);
     else hipLaunchKernelGGL((prefill_kernel<T, HD, true, WAVES, QC, MSUM, WIN>), grid, block, smem, st, *p, order, nqb, nsplit);
     launch_combine_rows(combine_rows_kernel<T, HD>, p, st, nsplit);
 }
@@ -285,12 +290,14 @@ static bool persistent_list(const vattn_attn_params* p) {
 
 // FP8 (vattn_fp8kv_prefill_with_kvcache; the caller checked its gate: no work list, no window, no prefill64): k_new / v_new are QUANTISED into
 // the cache first, the plan is the 2-byte call's without its prefill64 branch, the kernels are the FP8 builds
-template <typename T, int HD, bool FP8 = false> int launch_prefill_t(const vattn_attn_params* p, hipStream_t st, const fp8_scales sc = {}) {
+// CAP (vattn_softcap_attn_with_kvcache; the caller checked its gate: no work list, no rotation, no explicit prefill64): the 2-byte call — append, window
+// or not — on that same plan without prefill64 and the SOFTCAP builds
+template <typename T, int HD, bool FP8 = false, bool CAP = false> int launch_prefill_t(const vattn_attn_params* p, hipStream_t st, const fp8_scales sc = {}, const softcap_arg cap = {}) {
     if (p->k_new && p->seqlen_knew > 0) {
         if constexpr (FP8) launch_append_fp8(p, sc.k, sc.v, st);
         else launch_append(p, st);
     }
-    if constexpr (HD == 128 && !FP8) {
+    if constexpr (HD == 128 && !FP8 && !CAP) {
         if (p->pf_items) {        // host-planned work list: prefill64 pieces longest first, then the merge of the split blocks
             if (p->num_pf_items <= 0 || (p->num_pf_blocks > 0 && (!p->pf_blocks || !p->workspace)))
                 return fail(VATTN_K_ERR_INVALID, "pf_items needs num_pf_items, and pf_blocks + a workspace when blocks are split");
@@ -309,9 +316,13 @@ template <typename T, int HD, bool FP8 = false> int launch_prefill_t(const vattn
             return launch_status();
         }
     }
-    const PrefillPlan pl = plan_prefill(p, !FP8);
+    const PrefillPlan pl = plan_prefill(p, !FP8 && !CAP);
     if (pl.nsplit > 1 && !p->workspace) return fail(VATTN_K_ERR_INVALID, "KV-split prefill needs a workspace (vattn_attn_workspace_bytes)");
-    if constexpr (FP8) {
+    if constexpr (CAP) {
+        const bool win = p->window_left_plus1 > 0;
+        if (pl.tiling == 4) (win ? launch_prefill<T, HD, 4, 1, true, false, true> : launch_prefill<T, HD, 4, 1, false, false, true>)(p, st, pl.nsplit, {}, cap);
+        else (win ? launch_prefill<T, HD, 8, 1, true, false, true> : launch_prefill<T, HD, 8, 1, false, false, true>)(p, st, pl.nsplit, {}, cap);
+    } else if constexpr (FP8) {
         if (pl.tiling == 4) launch_prefill<T, HD, 4, 1, false, true>(p, st, pl.nsplit, sc);
         else launch_prefill<T, HD, 8, 1, false, true>(p, st, pl.nsplit, sc);
     } else {
@@ -324,8 +335,8 @@ template <typename T, int HD, bool FP8 = false> int launch_prefill_t(const vattn
         }
         // (a block that carries a sliding window takes the WIN builds, a window-less one the kernels it always ran)
         const bool win = p->window_left_plus1 > 0;
-        if (pl.tiling == 4) (win ? launch_prefill<T, HD, 4, 1, true> : launch_prefill<T, HD, 4, 1>)(p, st, pl.nsplit, {});
-        else (win ? launch_prefill<T, HD, 8, 1, true> : launch_prefill<T, HD, 8, 1>)(p, st, pl.nsplit, {});
+        if (pl.tiling == 4) (win ? launch_prefill<T, HD, 4, 1, true> : launch_prefill<T, HD, 4, 1>)(p, st, pl.nsplit, {}, {});
+        else (win ? launch_prefill<T, HD, 8, 1, true> : launch_prefill<T, HD, 8, 1>)(p, st, pl.nsplit, {}, {});
     }
     return launch_status();
 }
@@ -609,9 +620,16 @@ int launch_fp8kv_prefill_form(const vattn_attn_params* p, const float* k_scale, 
     if (p->d == 64) return f16 ? launch_prefill_t<_Float16, 64, true>(p, st, sc) : launch_prefill_t<__bf16, 64, true>(p, st, sc);
     return f16 ? launch_prefill_t<_Float16, 128, true>(p, st, sc) : launch_prefill_t<__bf16, 128, true>(p, st, sc);
 }
+// pre = softmax_scale / softcap in fp32, on the host (include/vattn_kernels.h, "Logit soft-capping")
+int launch_softcap_prefill_form(const vattn_attn_params* p, float softcap, hipStream_t st) {
+    const bool f16 = p->dtype == VATTN_DTYPE_F16;
+    const softcap_arg cap{p->softmax_scale / softcap, softcap};
+    if (p->d == 64) return f16 ? launch_prefill_t<_Float16, 64, false, true>(p, st, {}, cap) : launch_prefill_t<__bf16, 64, false, true>(p, st, {}, cap);
+    return f16 ? launch_prefill_t<_Float16, 128, false, true>(p, st, {}, cap) : launch_prefill_t<__bf16, 128, false, true>(p, st, {}, cap);
+}
 #endif
 
-// with_p64 = false: of the call over an fp8 cache (plan_prefill; its gate has refused a work list)
+// with_p64 = false: of the call over an fp8 cache, and of a soft-capped call (plan_prefill; their gates have refused a work list)
 static void describe_prefill(const vattn_attn_params* p, vattn_plan_desc* out, const bool with_p64) {
     out->form = 0;
     if (with_p64 && p->pf_items && p->d == 128) {

@@ -5,7 +5,12 @@
 Signature and semantics follow /root/reference/pod_attn/pod_attn/flash_attn_interface.py:1146-1291;
 the work is done by the gfx950 kernels in libvattn_amd.so through the C ABI
 (include/vattn_kernels.h) on torch's current HIP stream.  Arguments this path never uses (paged
-block_table, alibi, softcap, leftpad) raise NotImplementedError.
+block_table, alibi, leftpad) raise NotImplementedError.
+
+Logit soft-capping: `softcap=x` with x > 0 computes scores = x * tanh(q.k * softmax_scale / x) (Gemma-2 / Gemma-3) on builds of the decode
+and prefill kernels of their own (include/vattn_kernels.h, "Logit soft-capping"): one-token and multi-token decode, chunked / batched
+prefill, each with or without `window_size`.  The call takes the default launch (no work list, no host decode plan, no prefill64); a
+fused rotary table beside a cap raises NotImplementedError with the library's message (rotate first), x < 0 or non-finite ValueError.
 
 Sliding window: `window_size=(left, right)` selects causal local attention, bottom-right aligned as the
 reference states it — query row i of Sq rows over Lk visible keys attends keys
@@ -182,12 +187,27 @@ def relaunch(p, q_ptr: int, k_new_ptr: int, v_new_ptr: int, out_ptr: int, k_cach
     _issue(p, dev, *fast)
 
 
-def _issue(p, dev, lib, need=None, mask=None, scales=None, fp8_prefill=False):
+_FLT_MIN, _FLT_MAX = 1.1754943508222875e-38, 3.4028234663852886e+38
+
+
+def _softcap_value(softcap) -> float:
+    # the library takes the cap as a C float: 0, or a NORMAL fp32 number > 0 — above FLT_MAX it would arrive as inf (which the library calls an
+    # invalid argument), below FLT_MIN pre = softmax_scale / softcap overflows
+    x = float(softcap)
+    if not (x == 0.0 or _FLT_MIN <= x <= _FLT_MAX):      # (NaN fails every comparison)
+        raise ValueError("softcap must be 0 (no cap) or a finite fp32 number > 0 (%g <= softcap <= %g); got %r" % (_FLT_MIN, _FLT_MAX, softcap))
+    return x
+
+
+def _issue(p, dev, lib, need=None, mask=None, scales=None, fp8_prefill=False, softcap=0.0):
     """The one launch: the workspace the call needs (asked of the library unless `need` is known: relaunch) from the per-(device, stream)
     cache, the call on the current stream — the tree-masked entry point iff `mask` is given, the fp8-cache entry point iff `scales` =
     (k_scale, v_scale; either may be None: the library refuses that; fp8_prefill: its prefill-form sibling), the tree-masked entry point over
     an fp8 cache iff both are given — and its return code as an exception (the -10 of those entries names the rule of their gate that the
-    block breaks: NotImplementedError).  Returns the workspace need."""
+    block breaks: NotImplementedError), the soft-capped entry point iff `softcap` > 0 (never beside a mask or scales: there is no such entry).
+    Returns the workspace need."""
+    if need is None and softcap:
+        need = lib.vattn_softcap_attn_workspace_bytes(C.byref(p), softcap)
     if need is None:
         need = (lib.vattn_fp8kv_tree_attn_workspace_bytes if mask is not None and scales is not None else
                 lib.vattn_tree_attn_workspace_bytes if mask is not None else
@@ -196,7 +216,9 @@ def _issue(p, dev, lib, need=None, mask=None, scales=None, fp8_prefill=False):
     st = K.current_stream_ptr(dev)
     if need:
         p.workspace = _workspace(need, dev, st).data_ptr()   # kept alive by the per-(device, stream) cache until a larger one replaces it
-    if mask is not None and scales is not None:
+    if softcap:
+        rc = lib.vattn_softcap_attn_with_kvcache(C.byref(p), softcap, st)
+    elif mask is not None and scales is not None:
         rc = lib.vattn_fp8kv_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), *(s.data_ptr() if s is not None else None for s in scales), st)
     elif mask is not None:
         rc = lib.vattn_tree_attn_with_kvcache(C.byref(p), mask.data_ptr(), st)
@@ -206,7 +228,7 @@ def _issue(p, dev, lib, need=None, mask=None, scales=None, fp8_prefill=False):
     else:
         rc = lib.vattn_flash_attn_with_kvcache(C.byref(p), st)
     if rc != 0:
-        raise (NotImplementedError if (mask is not None or scales is not None) and rc == -10 else RuntimeError)(K.last_error(lib))
+        raise (NotImplementedError if (mask is not None or scales is not None or softcap) and rc == -10 else RuntimeError)(K.last_error(lib))
     return need
 
 
@@ -216,7 +238,8 @@ def _launch(p, dev, keep=()):
         _capture.append((p, keep))
         return
     lib = K.klib_for(p.variant)          # the product library; the lab build only for measurement variants (tests, kbench)
-    p._fast = (lib, _issue(p, dev, lib))      # relaunch(): same shapes, same plan
+    cap = getattr(p, "_softcap", 0.0)    # (set by the entry points beside the block: vattn_attn_params has no field for it)
+    p._fast = (lib, _issue(p, dev, lib, softcap=cap), None, None, False, cap)      # relaunch(): same shapes, same plan, same cap
 
 
 def _launch_tree(p, mask: torch.Tensor, dev, keep=()):
@@ -332,8 +355,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     rot = _rotary_table(rotary_cos, rotary_sin, _rotary_cos_sin, rotary_interleaved, q)
     if block_table is not None:
         raise NotImplementedError("paged KV (block_table) is what vAttention replaces; not supported")
-    if alibi_slopes is not None or cache_leftpad is not None or softcap != 0.0:
-        raise NotImplementedError("alibi / leftpad / softcap are not used by the vAttention path")
+    if alibi_slopes is not None or cache_leftpad is not None:
+        raise NotImplementedError("alibi / leftpad are not used by the vAttention path")
+    softcap = _softcap_value(softcap)
+    if softcap and _capture_active():
+        raise NotImplementedError("softcap cannot be combined with the fused hybrid launch")
     p, keep, out, lse, (B, Sq, Sk, Sn, D), dev = _build_block(q, k_cache, v_cache, k, v, cache_seqlens, cache_batch_idx, out, return_softmax_lse)
     # host-side bound on the sequences' lengths (sizes the prefill KV split): known when cache_seqlens is an int or the
     # caller (the attention wrapper, which has the lengths on the host) passes _max_seqlen_k; else the cache's row count
@@ -365,8 +391,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     plan = None
     # (a sliding window takes the default launch: its key walks are short and equal, the planners answer 0 for it and the library refuses
     # a list or host items beside one — include/vattn_kernels.h)
+    # (so does a soft-capped call: one more optional item beside the block, like the tree's mask and the fp8 scales — _issue picks its entry point)
     windowed = p.window_left_plus1 > 0
-    if Sq > 1 and not multitoken and D == 128 and num_splits == 0 and k is None and not _capture_active() and not windowed:
+    p._softcap = softcap
+    if Sq > 1 and not multitoken and D == 128 and num_splits == 0 and k is None and not _capture_active() and not windowed and not softcap:
         # prefill form: a work list for underfilled / unbalanced grids.  `_pf_plan`: a plan object built earlier for the same lengths
         # (this package's wrapper: one per iteration), else built here — and kept, keyed on the shapes and lengths: the L layers of an
         # iteration issue the same call — from the host-side lengths when there are any (_cache_seqlens_host, or the page manager's).
@@ -382,7 +410,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         counters["multitoken_decode_calls"] += 1
     elif Sq > 1:
         counters["prefill_calls"] += 1
-    if _cache_seqlens_host is not None and Sq == 1 and B > 1 and num_splits == 0 and not windowed and not torch.cuda.is_current_stream_capturing():
+    if _cache_seqlens_host is not None and Sq == 1 and B > 1 and num_splits == 0 and not windowed and not softcap and not torch.cuda.is_current_stream_capturing():
         # (the plan's tables travel by a host-to-device copy: not while the stream is being captured into a graph — the uniform split then)
         if _plan_tiles:                                        # (tests / A-B: pieces of exactly this many 32-key tiles)
             p.num_splits = -int(_plan_tiles)
@@ -691,13 +719,17 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wi
 def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q_lens: torch.Tensor, max_q_len: int,
                                    cache_seqlens: torch.Tensor, cache_batch_idx: Optional[torch.Tensor] = None,
                                    softmax_scale=None, causal=True, out=None, num_splits=0, _variant=0, _max_seqlen_k: int = 0,
-                                   _rotary_cos_sin=None, _pf_plan=None, window_size=(-1, -1)):
+                                   _rotary_cos_sin=None, _pf_plan=None, window_size=(-1, -1), softcap=0.0):
     """MI355X extension (SURVEY §8f "batched multi-prefill"): ONE launch for the prefill chunks of several sequences with
     different lengths.  q / out are the flattened tokens [T, Hq, D]; entry i attends with rows [q_start[i], q_start[i] +
     q_lens[i]) over cache slot cache_batch_idx[i] (identity if None), keys [0, cache_seqlens[i]) — the chunk's own K/V must
     already be in the cache (cache_flat).  Bottom-right-aligned causal mask per entry, exactly as flash_attn_with_kvcache
     does for one sequence (the reference's wrapper issues one call per prompt, vattention_flashattention_wrapper.py:129-174).
-    `window_size=(left, right)`: causal sliding window per entry, rules as flash_attn_with_kvcache."""
+    `window_size=(left, right)`: causal sliding window per entry, rules as flash_attn_with_kvcache.  `softcap` > 0: logit soft-capping, as
+    there (the default launch: no work list)."""
+    softcap = _softcap_value(softcap)
+    if softcap and _capture_active():
+        raise NotImplementedError("softcap cannot be combined with the fused hybrid launch")
     p, keep, out, dev = _build_varlen_block(q, k_cache, v_cache, q_start, q_lens, max_q_len, cache_seqlens, cache_batch_idx, out)
     T, Hq, D = q.shape
     Sk = k_cache.shape[1]
@@ -709,7 +741,8 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, q_start: torch.Tensor, q
     if _rotary_cos_sin is not None:      # q rows of entry i are rotated at positions (cache_seqlens[i] - q_lens[i]) + row
         rot = _rotary_table(None, None, _rotary_cos_sin, False, q)
         p.rotary_cos_sin, p.rotary_row_stride, p.rotary_dim = rot.data_ptr(), rot.stride(0), rot.shape[1]
-    if isinstance(_pf_plan, _PrefillPlan) and D == 128 and num_splits == 0 and not _capture_active() and not p.window_left_plus1:
+    p._softcap = softcap
+    if isinstance(_pf_plan, _PrefillPlan) and D == 128 and num_splits == 0 and not _capture_active() and not p.window_left_plus1 and not softcap:
         _pf_plan.attach(p)        # work list built from the host-side lengths of this iteration (prefill_plan)
     _launch(p, dev, keep=keep + (_rotary_cos_sin, _pf_plan))
     return out

@@ -127,6 +127,12 @@ def _bind(lib):
     lib.vattn_cache_keep_rows_fp8.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.vattn_cache_flat_fp8.restype = i32
     lib.vattn_cache_flat_fp8.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, i32, vp, vp, vp]
+    lib.vattn_softcap_attn_with_kvcache.restype = i32
+    lib.vattn_softcap_attn_with_kvcache.argtypes = [C.POINTER(AttnParams), C.c_float, vp]
+    lib.vattn_softcap_attn_workspace_bytes.restype = C.c_size_t
+    lib.vattn_softcap_attn_workspace_bytes.argtypes = [C.POINTER(AttnParams), C.c_float]
+    lib.vattn_softcap_attn_plan_describe.restype = i32
+    lib.vattn_softcap_attn_plan_describe.argtypes = [C.POINTER(AttnParams), C.c_float, C.POINTER(PlanDesc)]
     lib.vattn_decode_plan.restype = i32
     lib.vattn_decode_plan.argtypes = [C.POINTER(AttnParams), C.POINTER(i32), C.POINTER(DecodeItem), i32, C.POINTER(i32)]
     return lib
@@ -192,6 +198,16 @@ def describe_fp8kv_tree(p, lib=None) -> dict:
 
 def describe_tree(p, lib=None) -> dict:
     return describe(p, lib, tree=True)
+
+
+def describe_softcap(p, softcap: float, lib=None) -> dict:
+    """The launch plan of block `p` under logit soft-capping (vattn_softcap_attn_plan_describe): the plain call's plan for the same block
+    with its prefill64 branch skipped, or an error naming the rule of the gate the block breaks; softcap == 0: the plain call's plan."""
+    lib = lib or klib()
+    d = PlanDesc()
+    if lib.vattn_softcap_attn_plan_describe(C.byref(p), float(softcap), C.byref(d)) != 0:
+        raise RuntimeError(last_error(lib))
+    return {n: int(getattr(d, n)) for n, _ in d._fields_}
 
 
 def last_error(lib=None) -> str:
