@@ -36,6 +36,17 @@ extern "C" {
 
 #define VATTN_KERNELS_ABI 6u            /* bumped whenever vattn_attn_params changes */
 
+/* ROW-STRIDE CEILING of the K/V caches, in BYTES (k_row_stride / v_row_stride x 2, x 1 for an fp8 cache): 2^24 - 16.  The kernels rebase a
+ * 64-bit address per key tile and keep 32-bit byte offsets inside the tile; with S = the row's byte stride they form, in 32 bits,
+ *   decode (32-row tiles)                  31 S + row bytes per lane, 16 S steps, num_records 32 S             -> S <  2^27
+ *   register-staged prefill (64-row tiles) 63 S + row bytes per lane, num_records 64 S                          -> S <  2^26
+ *   prefill64 / prefill64p (64-row tiles)  the same, 64 S per tile step, and the persistent kernel's piece offsets
+ *                                          rows x S with a 24-BIT multiply (v_mad_u32_u24)                      -> S <  2^24
+ *   append / cache_flat / keep_rows        64-bit throughout                                                    -> no limit
+ * The host enforces the smallest for every call (strides are multiples of 16 bytes, hence - 16) and refuses a negative row stride: a
+ * wrapped offset would also wrap the bound that keeps the loads off unmapped pages. */
+#define VATTN_MAX_KV_ROW_STRIDE_BYTES ((int64_t)((1 << 24) - 16))
+
 typedef struct vattn_attn_params {
     /* sizeof(vattn_attn_params) and VATTN_KERNELS_ABI of the header the CALLER was built against.  The block grows between releases
      * (the plan fields below are extensions) and the kernels branch on pointers inside it: a caller built against an older header, or
@@ -48,7 +59,10 @@ typedef struct vattn_attn_params {
     void* out;
     int64_t q_batch_stride, q_row_stride, q_head_stride;
     int64_t o_batch_stride, o_row_stride, o_head_stride;
-    /* caches: [batch_cache, seqlen_k, h_k, d]; last dim contiguous, other strides arbitrary
+    /* caches: [batch_cache, seqlen_k, h_k, d]; last dim contiguous; batch and head strides any multiple of 8 elements (they enter
+     * 64-bit address arithmetic only: slots and rows may lie any number of GiB into the view); ROW-STRIDE CEILING: 0 <= k_row_stride,
+     * v_row_stride and row stride x bytes per cache element <= VATTN_MAX_KV_ROW_STRIDE_BYTES (below), else VATTN_K_ERR_UNSUPPORTED from
+     * every call, 0 from every _workspace_bytes entry and the error from every _plan_describe entry
      * (the decode call passes a [:, :max_cache_len] strided view) */
     void* k_cache;
     void* v_cache;

@@ -233,7 +233,18 @@ int launch_status() {
 // the caller's header and ours describe the same block (include/vattn_kernels.h)
 bool abi_ok(const vattn_attn_params* p) { return p && p->struct_size == (uint32_t)sizeof(vattn_attn_params) && p->abi_version == VATTN_KERNELS_ABI; }
 
-int validate(const vattn_attn_params* p) {
+// The row-stride ceiling of the caches (include/vattn_kernels.h, "ROW-STRIDE CEILING"): inside one key tile the kernels keep 32-bit byte offsets
+// against a per-tile 64-bit base — row x stride per lane, 16 x stride and 64 x stride steps, rows x stride as the descriptor's num_records —
+// and prefill64p forms its piece offsets with a 24-bit multiply of the row's byte stride (prefill64_common.h, piece_off).  kv_bytes: bytes per
+// cache element (2; an fp8 cache: 1).  A stride of 0 (one row broadcast) stays legal.
+static const char* kRowStride = "row-stride ceiling: k_row_stride / v_row_stride must be >= 0 and at most 2^24 - 16 BYTES (the kernels keep 32-bit byte "
+                                "offsets inside a key tile; prefill64 multiplies the row's byte stride in 24 bits)";
+static bool row_strides_ok(const vattn_attn_params* p, int kv_bytes) {
+    const int64_t lim = VATTN_MAX_KV_ROW_STRIDE_BYTES / kv_bytes;
+    return p->k_row_stride >= 0 && p->k_row_stride <= lim && p->v_row_stride >= 0 && p->v_row_stride <= lim;
+}
+
+int validate(const vattn_attn_params* p, int kv_bytes = 2) {
     if (!p) return fail(VATTN_K_ERR_INVALID, "null tensor pointer");
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library (zero the block, then set both from include/vattn_kernels.h)");
     if (!p->q || !p->out || !p->k_cache || !p->v_cache) return fail(VATTN_K_ERR_INVALID, "null tensor pointer");
@@ -257,6 +268,7 @@ int validate(const vattn_attn_params* p) {
                                p->k_head_stride, p->v_batch_stride, p->v_row_stride, p->v_head_stride};
     for (int64_t s : strides)
         if (s % 8 != 0) return fail(VATTN_K_ERR_UNSUPPORTED, "strides must be multiples of 8 elements (16-byte vector access)");
+    if (!row_strides_ok(p, kv_bytes)) return fail(VATTN_K_ERR_UNSUPPORTED, kRowStride);
     if (((uintptr_t)p->q | (uintptr_t)p->k_cache | (uintptr_t)p->v_cache | (uintptr_t)p->out) & 15)
         return fail(VATTN_K_ERR_UNSUPPORTED, "tensor base pointers must be 16-byte aligned");
     if (p->rotary_cos_sin) {
@@ -378,10 +390,25 @@ extern "C" {
 
 const char* vattn_kernels_last_error(void) { return g_err.c_str(); }
 
-size_t vattn_attn_workspace_bytes(const vattn_attn_params* p) {
+// the plain call's workspace need / plan of a block whose row strides the caller has checked for ITS cache element size (row_strides_ok)
+static size_t plain_workspace_bytes(const vattn_attn_params* p) {
     if (!abi_ok(p)) return 0;
     if (!p || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0) return 0;
     return decode_form(p) ? decode_workspace_bytes(p) : prefill_workspace_bytes(p);
+}
+static int plain_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
+    if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
+    if (!p || !out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || (p->d != 64 && p->d != 128)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_plan_describe: bad shape");
+    memset(out, 0, sizeof *out);
+    if (decode_form(p)) decode_describe(p, out);
+    else prefill_describe(p, out);
+    out->workspace_bytes = (int64_t)plain_workspace_bytes(p);
+    return VATTN_K_OK;
+}
+
+size_t vattn_attn_workspace_bytes(const vattn_attn_params* p) {
+    if (!abi_ok(p) || !row_strides_ok(p, 2)) return 0;
+    return plain_workspace_bytes(p);
 }
 
 int vattn_flash_attn_with_kvcache(const vattn_attn_params* p, void* stream) {
@@ -410,20 +437,20 @@ int vattn_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_t* tre
 // The tree-masked call runs the multi-token launch of the same block on other builds of the same kernels: same planners, same answers.
 size_t vattn_tree_attn_workspace_bytes(const vattn_attn_params* p) {
     if (!abi_ok(p) || p->window_left_plus1 > 0 || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || tree_gate_reason(p)) return 0;
-    return vattn_attn_workspace_bytes(p);
+    return vattn_attn_workspace_bytes(p);      // (checks the row strides)
 }
 
 int vattn_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);
     if (const char* why = tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
-    return vattn_attn_plan_describe(p, out);
+    return vattn_attn_plan_describe(p, out);      // (checks the row strides)
 }
 
 int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream) {
     if (!abi_ok(p)) return validate(p);
     if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the fp8 rule)
-    int rc = validate(p);
+    int rc = validate(p, 1);      // (fp8: strides in bytes)
     if (rc) return rc;
     if ((rc = fp8kv_check_args(p, k_scale, v_scale))) return rc;
 #ifndef VATTN_LAB
@@ -435,14 +462,15 @@ int vattn_fp8kv_attn_with_kvcache(const vattn_attn_params* p, const float* k_sca
 
 // The call over an fp8 cache runs the launch of the same block on other builds of the same kernels: same planners, same answers.
 size_t vattn_fp8kv_attn_workspace_bytes(const vattn_attn_params* p) {
-    if (!abi_ok(p) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || fp8kv_gate_reason(p)) return 0;
-    return vattn_attn_workspace_bytes(p);
+    if (!abi_ok(p) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || fp8kv_gate_reason(p) || !row_strides_ok(p, 1)) return 0;
+    return plain_workspace_bytes(p);
 }
 
 int vattn_fp8kv_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (const char* why = fp8kv_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
-    return vattn_attn_plan_describe(p, out);
+    if (!row_strides_ok(p, 1)) return fail(VATTN_K_ERR_UNSUPPORTED, kRowStride);
+    return plain_plan_describe(p, out);
 }
 
 int vattn_fp8kv_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_t* tree_mask, const float* k_scale, const float* v_scale, void* stream) {
@@ -450,7 +478,7 @@ int vattn_fp8kv_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_
     if (!abi_ok(p)) return validate(p);
     if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);      // (as in the 2-byte tree call; before the gates: the fp8 gate would call it unsupported)
     if (const char* why = fp8kv_tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the rule)
-    int rc = validate(p);
+    int rc = validate(p, 1);      // (fp8: strides in bytes)
     if (rc) return rc;
     if ((rc = fp8kv_check_args(p, k_scale, v_scale))) return rc;
 #ifndef VATTN_LAB
@@ -463,21 +491,22 @@ int vattn_fp8kv_tree_attn_with_kvcache(const vattn_attn_params* p, const uint32_
 // The tree-masked call over an fp8 cache runs the multi-token launch of the same block on other builds of the same kernels: what
 // vattn_tree_attn_workspace_bytes / _plan_describe answer.
 size_t vattn_fp8kv_tree_attn_workspace_bytes(const vattn_attn_params* p) {
-    if (!abi_ok(p) || p->window_left_plus1 > 0 || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || fp8kv_tree_gate_reason(p)) return 0;
-    return vattn_attn_workspace_bytes(p);
+    if (!abi_ok(p) || p->window_left_plus1 > 0 || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || fp8kv_tree_gate_reason(p) || !row_strides_ok(p, 1)) return 0;
+    return plain_workspace_bytes(p);
 }
 
 int vattn_fp8kv_tree_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (p->window_left_plus1 > 0) return fail(VATTN_K_ERR_INVALID, kTreeWindow);
     if (const char* why = fp8kv_tree_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
-    return vattn_attn_plan_describe(p, out);
+    if (!row_strides_ok(p, 1)) return fail(VATTN_K_ERR_UNSUPPORTED, kRowStride);
+    return plain_plan_describe(p, out);
 }
 
 int vattn_fp8kv_prefill_with_kvcache(const vattn_attn_params* p, const float* k_scale, const float* v_scale, void* stream) {
     if (!abi_ok(p)) return validate(p);
     if (const char* why = fp8kv_prefill_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);      // (before validate: the refusal names the fp8 rule)
-    int rc = validate(p);
+    int rc = validate(p, 1);      // (fp8: strides in bytes)
     if (rc) return rc;
     if ((rc = fp8kv_check_args(p, k_scale, v_scale))) return rc;
 #ifndef VATTN_LAB
@@ -489,7 +518,7 @@ int vattn_fp8kv_prefill_with_kvcache(const vattn_attn_params* p, const float* k_
 
 // The prefill call over an fp8 cache takes the 2-byte call's plan without its prefill64 branch (prefill_kernels.hip, plan_prefill): tiling 1 or 4
 size_t vattn_fp8kv_prefill_workspace_bytes(const vattn_attn_params* p) {
-    if (!abi_ok(p) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || fp8kv_prefill_gate_reason(p)) return 0;
+    if (!abi_ok(p) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || fp8kv_prefill_gate_reason(p) || !row_strides_ok(p, 1)) return 0;
 #ifndef VATTN_LAB
     return fp8kv_prefill_workspace_bytes(p);
 #else
@@ -500,6 +529,7 @@ size_t vattn_fp8kv_prefill_workspace_bytes(const vattn_attn_params* p) {
 int vattn_fp8kv_prefill_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (const char* why = fp8kv_prefill_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    if (!row_strides_ok(p, 1)) return fail(VATTN_K_ERR_UNSUPPORTED, kRowStride);
     if (!out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0) return fail(VATTN_K_ERR_INVALID, "vattn_fp8kv_prefill_plan_describe: bad shape");
 #ifndef VATTN_LAB
     memset(out, 0, sizeof *out);
@@ -531,7 +561,7 @@ int vattn_softcap_attn_with_kvcache(const vattn_attn_params* p, float softcap, v
 // over an fp8 cache (prefill_kernels.hip, plan_prefill): same planners, same answers, nothing tuned apart.
 size_t vattn_softcap_attn_workspace_bytes(const vattn_attn_params* p, float softcap) {
     if (softcap == 0.0f) return vattn_attn_workspace_bytes(p);
-    if (!softcap_ok(softcap) || !abi_ok(p) || !softcap_pre_ok(p, softcap) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || softcap_gate_reason(p)) return 0;
+    if (!softcap_ok(softcap) || !abi_ok(p) || !softcap_pre_ok(p, softcap) || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || softcap_gate_reason(p) || !row_strides_ok(p, 2)) return 0;
 #ifndef VATTN_LAB
     return decode_form(p) ? decode_workspace_bytes(p) : fp8kv_prefill_workspace_bytes(p);
 #else
@@ -545,6 +575,7 @@ int vattn_softcap_attn_plan_describe(const vattn_attn_params* p, float softcap, 
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
     if (!softcap_pre_ok(p, softcap)) return fail(VATTN_K_ERR_INVALID, kSoftcapPre);
     if (const char* why = softcap_gate_reason(p)) return fail(VATTN_K_ERR_UNSUPPORTED, why);
+    if (!row_strides_ok(p, 2)) return fail(VATTN_K_ERR_UNSUPPORTED, kRowStride);
     if (!out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0) return fail(VATTN_K_ERR_INVALID, "vattn_softcap_attn_plan_describe: bad shape");
 #ifndef VATTN_LAB
     memset(out, 0, sizeof *out);
@@ -559,12 +590,8 @@ int vattn_softcap_attn_plan_describe(const vattn_attn_params* p, float softcap, 
 
 int vattn_attn_plan_describe(const vattn_attn_params* p, vattn_plan_desc* out) {
     if (!abi_ok(p)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_params: struct_size / abi_version do not match this library");
-    if (!p || !out || p->h_k <= 0 || p->h <= 0 || p->b <= 0 || p->seqlen_q <= 0 || (p->d != 64 && p->d != 128)) return fail(VATTN_K_ERR_INVALID, "vattn_attn_plan_describe: bad shape");
-    memset(out, 0, sizeof *out);
-    if (decode_form(p)) decode_describe(p, out);
-    else prefill_describe(p, out);
-    out->workspace_bytes = (int64_t)vattn_attn_workspace_bytes(p);
-    return VATTN_K_OK;
+    if (!row_strides_ok(p, 2)) return fail(VATTN_K_ERR_UNSUPPORTED, kRowStride);
+    return plain_plan_describe(p, out);
 }
 
 int32_t vattn_decode_plan(const vattn_attn_params* p, const int32_t* cache_seqlens_host, vattn_decode_item* items_out, int32_t cap, int32_t* seq_out) {
