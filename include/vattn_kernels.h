@@ -76,7 +76,9 @@ typedef struct vattn_attn_params {
     const int32_t* cache_seqlens;     /* int32[b] on device, or NULL: every sequence uses seqlen_k      */
     const int32_t* cache_batch_idx;   /* int32[b] on device, or NULL: identity                          */
     float* softmax_lse;               /* optional float[b, h, seqlen_q] (natural log), or NULL          */
-    /* split-KV workspace; sized by vattn_attn_workspace_bytes, may be NULL if that returns 0 */
+    /* split-KV workspace; sized by vattn_attn_workspace_bytes, may be NULL if that returns 0.  Its contents on entry are arbitrary, the call
+     * writes only inside [workspace, workspace + workspace_bytes), and the results do not depend on the prior contents
+     * (tests/test_gpu_workspace.py; vattn_hybrid_attn's zeroed workspace is the one exception). */
     void* workspace;
     /* batched prefill of several sequences with DIFFERENT chunk lengths (MI355X extension; both NULL otherwise): q / out are
      * then [total_tokens, h, d] (q_batch_stride / o_batch_stride ignored), batch entry i owns rows
